@@ -8,16 +8,23 @@ features and masks on the GPU, seed-exact with the reference).
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     python bench.py --config c3        # BASELINE config 3 alone (TSP n=128 complete, 16 384 slots); c4 = SteinerTree n=256 m=1024; c5 = mixed ragged
 
+    python bench.py --full             # everything below the headline too (reference window, rooflines, configs, CPU baselines)
+    python bench.py --dump-outputs bench_outputs   # the last timed step's outputs as bench_outputs/<name>.npy, to compare builds
+
 One JSON line on rank 0.  `value` = (envs x steps over all ranks) / max-over-ranks wall time, inputs resident
 in HBM.  Whatever --warmup says, the engine first runs SETTLE untimed steps (more than the longest episode), so the
 timed window is the steady state of the autoreset loop and not the transient that follows a full reset; the line
-reports the resets per step inside the timed window beside a reference window and flags a non-stationary one.
+reports the resets per step inside the timed window.  A plain run stops there.  With --full it goes on, outside the
+timed region: a reference window and a flag for a non-stationary timed one, and the figures below.
 `roofline` is the step kernel (HBM-bound; algorithmic bytes per env-step from SURVEY 8d) timed with HIP events on its
 stream; `roofline_1m` the same kernel at 1 M slots (where the launch floor no longer hides the memory system);
 `roofline_reset` the reset path's issue-rate evidence (rocprofv3 SQ counters, profiles/); `cpu_baseline` is the CPU
 oracle (a port of the reference semantics, not the reference) on the host cores, rank 0, N=1 only.
 `configs` (N=1, config c2 only, measured AFTER the contract's timed region): BASELINE configs 3, 4 and 5 on the same GPU, each
 with its own value, step-kernel roofline and bounded cpu_baseline.
+--dump-outputs: rank 0's slots, right after the timed window, as float32 / float64 arrays of what step() would hand a caller:
+reward, flags, costs and episode lengths of every slot (of a seeded sample beyond DUMP_SCALAR_SLOTS), observation and action
+mask of a fixed, seeded sample of slots (at most DUMP_VECTOR_BYTES).  The inputs are seeded: equal arguments, equal inputs.
 """
 import argparse
 import json
@@ -33,6 +40,9 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
 SETTLE = 128           # untimed steps in front of the warm-up: > 2 x the longest ShortestPath episode at n = 64
 PROFILE_TAGS = ("r04", "r03", "r02")
+DUMP_SCALAR_SLOTS = 1 << 18     # --dump-outputs: per-slot results of at most this many slots (8 float64 arrays: <= 16 MB)
+DUMP_SAMPLE_SLOTS = 4096        # observation and mask of at most this many slots ...
+DUMP_VECTOR_BYTES = 40 << 20    # ... and at most this many bytes of them
 
 # BASELINE.json configs that fit one GPU.  algo_bytes: SURVEY.md 8(d), canonical 32-bit CSR + byte mask, per env-step.
 CONFIGS = {
@@ -89,6 +99,52 @@ def step_kernel_us(env, reps=9, burst=5, seed0=2000):
         env.reset(seed=seed0 + rep)
         vals.append((env.timed_step_burst_raw_ms(burst, policy_seed=2) - empty) * 1e3 / burst)
     return sorted(vals)[len(vals) // 2]
+
+
+def _sample(B, k):
+    """a fixed, seeded choice of k of the B slots (all of them when k >= B), in slot order"""
+    import numpy as np
+    return np.arange(B) if k >= B else np.sort(np.random.default_rng(0).choice(B, k, replace=False))
+
+
+def dump_outputs(env, out_dir):
+    """the outputs of the last step that ran, as DIR/<name>.npy: per-slot results of every engine in slot order (a VectorGraphEnv, a
+    ShardedVectorEnv's shards or a MixedVectorEnv's members), and for uniform engines the observation and the action mask of a sample"""
+    import numpy as np
+    import torch
+    members = getattr(env, "members", [env])
+    ragged = hasattr(members[0], "classes")
+    slabs = lambda m: m.g if ragged else m.t
+    B = sum(m.num_envs for m in members)
+
+    def pick(f, keep, dtype):
+        """rows `keep` (slot numbers, ascending) of the per-slot tensor f(member, its local rows), over the members in slot order"""
+        out, base = [], 0
+        for m in members:
+            loc = keep[(keep >= base) & (keep < base + m.num_envs)] - base
+            out.append(f(m, torch.as_tensor(loc, device=m.device)).cpu().numpy())
+            base += m.num_envs
+        return np.concatenate(out).astype(dtype)
+
+    keep = _sample(B, DUMP_SCALAR_SLOTS)
+    arrays = {"slots": keep.astype(np.float64)}
+    for name, key in (("reward", "reward"), ("terminated", "terminated"), ("solved", "solved"), ("solution_cost", "final_cost"),
+                      ("heuristic_solution", "final_heur"), ("invalid_action", "invalid"), ("episode_length", "final_len")):
+        arrays[name] = pick(lambda m, r: slabs(m)[key][r], keep, np.float64)
+    if not ragged:  # (a ragged batch's observation and mask differ in size from class to class)
+        m0 = members[0]
+        n, F, E, Fe = m0.n, m0.F, m0.E, m0.Fe
+        keep = _sample(B, min(DUMP_SAMPLE_SLOTS, DUMP_VECTOR_BYTES // (4 * (n * F + E * (Fe + 2) + m0.mask.shape[1]))))
+        arrays["sample_slots"] = keep.astype(np.float64)
+        arrays["mask"] = pick(lambda m, r: m.mask[r], keep, np.float32)
+        arrays["obs_x"] = pick(lambda m, r: m.t["x"].view(m.num_envs, n, F)[r], keep, np.float32)
+        arrays["obs_edge_attr"] = pick(lambda m, r: m.t["edge_attr"].view(m.num_envs, E, Fe)[r], keep, np.float32)
+        # local node ids (VectorGraphEnv.edge_links of the sampled slots): they do not depend on how the batch is sharded
+        arrays["obs_edge_links"] = pick(lambda m, r: (m.t["edge_index"].view(2, m.num_envs, E)[:, r] - (r * n + m.node_id_base).view(1, -1, 1))
+                                        .permute(1, 2, 0), keep, np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def load_profile():
@@ -181,20 +237,23 @@ def measure_c5(ge, torch, cfg, args, dev, rank, world, barrier, prof):
     barrier()
     dt = time.perf_counter() - t0
     episodes = eps() - ep0
-    # step kernel of every member inside its own loop (HIP events on the launch stream)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(mixed, args.dump_outputs)
+    # --full: step kernel of every member inside its own loop (HIP events on the launch stream)
     rl = []
-    for m, (env_id, _, algo) in zip(members, labels):
-        tm = m.timed_rollout(30, policy_seed=1)
-        us = tm["step_ms"] * 1e3 / 30
-        ach = algo * m.num_envs / (us * 1e-6) / 1e9
-        rl.append({"member": env_id, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
-                   "traffic": None, "algorithmic_bytes_per_launch": algo * m.num_envs, "avg_launch_us": us,
-                   "avg_launch_us_method": "HIP events around every step launch of 30 loop steps (includes ~2 us of event-pair overhead)",
-                   "autoreset_ms_per_step": tm["reset_ms"] / 30, "size_classes": len(m.classes)})
+    if args.full:
+        for m, (env_id, _, algo) in zip(members, labels):
+            tm = m.timed_rollout(30, policy_seed=1)
+            us = tm["step_ms"] * 1e3 / 30
+            ach = algo * m.num_envs / (us * 1e-6) / 1e9
+            rl.append({"member": env_id, "bound": "hbm", "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": ach / HBM_PEAK_GBS,
+                       "traffic": None, "algorithmic_bytes_per_launch": algo * m.num_envs, "avg_launch_us": us,
+                       "avg_launch_us_method": "HIP events around every step launch of 30 loop steps (includes ~2 us of event-pair overhead)",
+                       "autoreset_ms_per_step": tm["reset_ms"] / 30, "size_classes": len(m.classes)})
     for m in members:
         m.g["work_count"]  # (slabs stay referenced until close)
     mixed.close()
-    return dt, steps, B, episodes, settle, rl, [m.prefetch for m in members]
+    return dt, steps, B, episodes, settle, rl, [m.prefetch for m in members], [label for label, _, _ in labels]
 
 
 def measure_uniform(ge, torch, name, cfg, args, dev, rank, world, barrier, reduce_max, prof, prof_src, emu=None):
@@ -224,17 +283,10 @@ def measure_uniform(ge, torch, name, cfg, args, dev, rank, world, barrier, reduc
     episodes = total("episode") - ep0
     assert total("tstep") == B * (steps + args.warmup + settle)
     value = world * B * steps / dt
-    # reference window (outside the contract's timed region): 200 more steps, timed the same way -- the steady-state figure beside
-    # a short driver window -- and their reset rate, to judge the timed window against
-    REF = (200 if name == "c2" else steps) if emu is None else steps
-    barrier()
-    t1 = time.perf_counter()
-    env.random_rollout(REF, policy_seed=1)
-    barrier()
-    value_ref = B * REF / (time.perf_counter() - t1)  # this rank's slots only
-    ref_rate = (total("episode") - ep0 - episodes) / REF
-    rate = episodes / steps
     env.check_device_errors()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(env, args.dump_outputs)
+    rate = episodes / steps
     out = {
         "metric": cfg["metric"],
         "value": value, "unit": "env-steps/s", "n_gpus": world, "steps": steps, "warmup": args.warmup,
@@ -244,10 +296,24 @@ def measure_uniform(ge, torch, name, cfg, args, dev, rank, world, barrier, reduc
                                "(seed-exact G(n,m)+features on device)" % (cfg["workload"], B),
                    "envs_per_gpu": B, "shards": shards, "prefetch_period": env.prefetch, "episodes_finished_per_gpu": episodes, "settle_steps": settle,
                    "parallelism": "batch shard x%d, no collective" % world},
-        "resets_per_step": rate, "resets_per_step_reference_window": ref_rate,
-        "window_stationary": bool(ref_rate > 0 and abs(rate / ref_rate - 1.0) <= 0.10),
-        "value_200": value_ref * world, "value_200_steps": REF,
+        "resets_per_step": rate,
     }
+    if not args.full:
+        env.close()
+        return out
+    # reference window (outside the contract's timed region): 200 more steps, timed the same way -- the steady-state figure beside
+    # a short driver window -- and their reset rate, to judge the timed window against
+    REF = (200 if name == "c2" else steps) if emu is None else steps
+    barrier()
+    t1 = time.perf_counter()
+    env.random_rollout(REF, policy_seed=1)
+    barrier()
+    value_ref = B * REF / (time.perf_counter() - t1)  # this rank's slots only
+    ref_rate = (total("episode") - ep0 - episodes) / REF
+    env.check_device_errors()
+    out.update({"resets_per_step_reference_window": ref_rate,
+                "window_stationary": bool(ref_rate > 0 and abs(rate / ref_rate - 1.0) <= 0.10),
+                "value_200": value_ref * world, "value_200_steps": REF})
     if emu is not None:  # rehearsal of the launcher on the CPU harness: the loop above is all there is to rehearse
         env.close()
         return out
@@ -306,6 +372,9 @@ def main():
     ap.add_argument("--shards", type=int, default=0, help="independent engines the batch of a GPU is split into, each on its own HIP stream (default: the config's; 1 = one engine)")
     ap.add_argument("--serial-shards", action="store_true", help="diagnostic (counter collection): the shards one after the other on one stream, so that a launch's counters are its own")
     ap.add_argument("--prefetch", type=int, default=-1, help="episode prefetch: refill period in steps, 0 = regenerate in place (default: the engine's choice for the config)")
+    ap.add_argument("--full", action="store_true", help="after the headline: reference window, rooflines, the `configs` block and the CPU "
+                    "baselines (the --no-* options below leave parts of it out); without it the run stops after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy (rank 0's slots)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-1m", action="store_true", help="skip the 1 M-slot step-kernel roofline leg")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` block (BASELINE configs 3-5 behind the headline line)")
@@ -364,26 +433,28 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return float(tt.item())
 
-    prof, prof_src = load_profile() if emu is None else ({}, None)
+    prof, prof_src = load_profile() if emu is None and args.full else ({}, None)
     cfg = CONFIGS[args.config]
-    single = rank == 0 and world == 1 and emu is None
+    single = rank == 0 and world == 1 and emu is None and args.full  # (the legs behind the headline that run on rank 0 of one GPU)
 
     def c5_line(sub_args):
-        dt, steps, B, episodes, settle, rl, pf = measure_c5(ge, torch, CONFIGS["c5"], sub_args, dev, rank, world, barrier, prof)
+        dt, steps, B, episodes, settle, rl, pf, engines = measure_c5(ge, torch, CONFIGS["c5"], sub_args, dev, rank, world, barrier, prof)
         dt = reduce_max(dt)
         c = CONFIGS["c5"]
-        return {"metric": c["metric"], "value": world * B * steps / dt, "unit": "env-steps/s", "n_gpus": world, "steps": steps, "warmup": sub_args.warmup,
+        line = {"metric": c["metric"], "value": world * B * steps / dt, "unit": "env-steps/s", "n_gpus": world, "steps": steps, "warmup": sub_args.warmup,
                 "ms_per_step": dt * 1e3 / steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
                 "config": {"workload": c["workload"], "envs_per_gpu": B, "prefetch_period": pf, "episodes_finished_per_gpu": episodes, "settle_steps": settle,
-                           "parallelism": "batch shard x%d, no collective" % world, "launch_sequences_per_step": len(rl), "engines": [r["member"] for r in rl]},
-                "resets_per_step": episodes / steps,
-                "roofline": max(rl, key=lambda r: r["avg_launch_us"]), "roofline_members": rl}
+                           "parallelism": "batch shard x%d, no collective" % world, "launch_sequences_per_step": len(engines), "engines": engines},
+                "resets_per_step": episodes / steps}
+        if rl:
+            line.update({"roofline": max(rl, key=lambda r: r["avg_launch_us"]), "roofline_members": rl})
+        return line
 
     if args.config == "c5":
         out = c5_line(args)
     else:
         out = measure_uniform(ge, torch, args.config, cfg, args, dev, rank, world, barrier, reduce_max, prof, prof_src, emu)
-    if "reset_path" in prof and args.config == "c2":
+    if "reset_path" in prof and args.config == "c2":  # (prof is empty without --full)
         out["roofline_reset"] = prof["reset_path"]  # SQ-counter issue rates of the feature / graph kernels (tools/pmc_sq_passes.sh)
         out["roofline_reset_source"] = prof_src
     if single and args.config == "c2" and not args.no_1m:
@@ -405,6 +476,7 @@ def main():
         block = {}
         for name in ("c3", "c4", "c5"):
             sub = argparse.Namespace(**vars(args)); sub.steps = 0; sub.envs = 0; sub.prefetch = -1; sub.shards = 0; sub.config = name
+            sub.dump_outputs = None  # (the dump is the headline's)
             try:
                 torch.cuda.empty_cache()
                 block[name] = c5_line(sub) if name == "c5" else measure_uniform(ge, torch, name, CONFIGS[name], sub, dev, rank, world, barrier, reduce_max, prof, prof_src)

@@ -29,6 +29,29 @@ def test_bench_gpus_2_launches_its_own_ranks():
     assert abs(out["value"] - 2 * 12 * 3 / (out["ms_per_step"] * 3e-3)) < 1e-6 * out["value"]
 
 
+def test_bench_plain_full_and_dump_outputs(tmp_path):
+    """A plain run prints the headline and stops after the timed steps; --full adds the reference window.  --dump-outputs writes the
+    outputs of the last timed step as float32 / float64 .npy files, and equal arguments give equal files."""
+    import numpy as np
+    args = ["--emu", "--envs", "12", "--steps", "3", "--warmup", "1"]
+    for k in (1, 2):
+        r = _run(args + ["--dump-outputs", str(tmp_path / str(k))])
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads(r.stdout.strip().splitlines()[-1])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and "value_200" not in out
+    names = sorted(os.listdir(tmp_path / "1"))
+    assert names == sorted(os.listdir(tmp_path / "2"))
+    assert {"reward.npy", "terminated.npy", "mask.npy", "obs_x.npy", "obs_edge_links.npy"} <= set(names)
+    for name in names:
+        a, b = np.load(tmp_path / "1" / name), np.load(tmp_path / "2" / name)
+        assert a.dtype in (np.float32, np.float64) and len(a) == 12, name
+        assert np.array_equal(a, b), name
+    r = _run(args + ["--full"])
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 3 and "value_200" in out and "window_stationary" in out
+
+
 def test_bench_refuses_a_world_size_that_contradicts_gpus():
     r = _run(["--emu", "--gpus", "2", "--envs", "4", "--steps", "1", "--warmup", "0"], env=dict(WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"))
     assert r.returncode != 0 and "WORLD_SIZE" in r.stderr

@@ -3,5 +3,5 @@
 TAG=${1:-r03}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/${TAG}_prof; mkdir -p $O
 cd $R
-timeout -k 10 400 python3 bench.py > $O/bench_c2.json 2> $O/bench_c2.err
+timeout -k 10 400 python3 bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err
 cut -c1-400 $O/bench_c2.json
