@@ -25,6 +25,7 @@ struct GeBucket {
   int reset_lds, reset_grid;                     // graph kernel
   int gen_lds, gen_pre_off, gen_waves, gen_grid;  // generic feature kernel (classes with n > 64)
   bool gen_used;
+  int fb_lds, fb_pre_off;  // a bucket of classes with n <= 64 only: the generic kernel for the fast path's fallback list (slots too deep for it)
 };
 static int bucket_of(int n) { return n <= 128 ? 0 : (n <= 256 ? 1 : (n <= 512 ? 2 : 3)); }
 
@@ -41,6 +42,7 @@ struct ge_engine {
   // n / m / W = the widest class) and R names the device copy of the class table
   int n_classes;
   GeRagged R;
+  int aw_max;     // multi-class engine: the widest mask row over the classes (edge-action envs: 2 m words, not a function of n)
   std::vector<GeParams> classes;  // host copy (ge_vectorize launches per class)
   int feat64_pre_off, gen_pre_off;
   int lds_bytes_inject;  // GeParams.nocolw engines: ge_inject_state runs the graph kernel on the full LDS carve (the injected rows need the list)
@@ -177,15 +179,6 @@ static int derive(const ge_config *cfg, GeParams &P, int queue_B = 0) {
   return GE_OK;
 }
 
-// per-slot work space of the sequential is_eval_env baselines (ge_tsp_eval.h); 0 = none
-static uint64_t eval_slot_bytes(const GeParams &P) {
-  if (!P.is_eval) return 0;
-  if (P.env_type == GE_TSP) return ge_ch_slot_bytes(P.n);
-  if (P.env_type == GE_MAX_INDEPENDENT_SET && !P.weighted) return ge_cr_slot_bytes(P.n, P.m);
-  if (P.env_type == GE_STEINER_TREE && P.n_dests > 1 && P.n_dests < P.n - 1) return ge_steiner_slot_bytes(P.n, P.m, P.T);  // steiner_tree.py:78-87: the Kou branch
-  return 0;
-}
-
 extern "C" int ge_get_layout(const ge_config *cfg, ge_layout *out) {
   GeParams P;
   int rc = derive(cfg, P);
@@ -203,14 +196,22 @@ extern "C" int ge_get_layout(const ge_config *cfg, ge_layout *out) {
 
 extern "C" int ge_destroy(ge_engine *e);
 
-// the multi-class engine is instantiated for the env ids of BASELINE config 5 (ShortestPath, DensestSubgraph, MaxIndependentSet)
-#define GE_FOR_RAGGED_ENV(env_type, stmt)                                                   \
-  do {                                                                                      \
-    switch (env_type) {                                                                     \
-      case GE_SHORTEST_PATH: { constexpr int ENV = GE_SHORTEST_PATH; stmt; break; }           \
-      case GE_DENSEST_SUBGRAPH: { constexpr int ENV = GE_DENSEST_SUBGRAPH; stmt; break; }     \
-      default: { constexpr int ENV = GE_MAX_INDEPENDENT_SET; stmt; break; }                   \
-    }                                                                                       \
+// the multi-class engine is instantiated for every env id; each case is explicit (the config-5 ids -- ShortestPath, DensestSubgraph,
+// MaxIndependentSet -- keep the instantiations they had when they were the only ones)
+#define GE_FOR_RAGGED_ENV(env_type, stmt)                                                           \
+  do {                                                                                              \
+    switch (env_type) {                                                                             \
+      case GE_SHORTEST_PATH: { constexpr int ENV = GE_SHORTEST_PATH; stmt; break; }                   \
+      case GE_LONGEST_PATH: { constexpr int ENV = GE_LONGEST_PATH; stmt; break; }                     \
+      case GE_STEINER_TREE: { constexpr int ENV = GE_STEINER_TREE; stmt; break; }                     \
+      case GE_TSP: { constexpr int ENV = GE_TSP; stmt; break; }                                       \
+      case GE_DENSEST_SUBGRAPH: { constexpr int ENV = GE_DENSEST_SUBGRAPH; stmt; break; }             \
+      case GE_MULTICAST_ROUTING: { constexpr int ENV = GE_MULTICAST_ROUTING; stmt; break; }           \
+      case GE_DISTRIBUTION_CENTER: { constexpr int ENV = GE_DISTRIBUTION_CENTER; stmt; break; }       \
+      case GE_PERISHABLE_DELIVERY: { constexpr int ENV = GE_PERISHABLE_DELIVERY; stmt; break; }       \
+      case GE_MAX_INDEPENDENT_SET: { constexpr int ENV = GE_MAX_INDEPENDENT_SET; stmt; break; }       \
+      default: break;                                                                               \
+    }                                                                                               \
   } while (0)
 
 static int check_buffers(const GeParams &P, const ge_buffers *bufs) {
@@ -234,6 +235,9 @@ static int check_buffers(const GeParams &P, const ge_buffers *bufs) {
   return GE_OK;
 }
 
+static bool edge_quad(const ge_engine *e);
+static size_t edge_lds(const ge_engine *e);
+
 // launch geometry and LDS limits from e->P (uniform engine) or from the class table (multi-class engine); deletes e on failure
 static int finish_create(ge_engine *e, ge_engine **out) {
   const GeParams &P = e->P;
@@ -246,7 +250,7 @@ static int finish_create(ge_engine *e, ge_engine **out) {
   for (const GeParams &C : e->classes) {
     if (C.lds.total > reset_lds) reset_lds = C.lds.total;
     if (C.ldsf.total > gen_lds) gen_lds = C.ldsf.total;
-    if (C.n <= 64) { any64 = true; const int b = ge_f64_pre_off(C.E, 0, nblk); if (b > f64_body) f64_body = b; }
+    if (C.n <= 64 && !C.spatial) { any64 = true; const int b = ge_f64_pre_off(C.E, C.env_type == GE_TSP, nblk); if (b > f64_body) f64_body = b; }
   }
   if (rg && e->P.lds.pre != 0) { e->P.lds.pre = ge_align16(reset_lds); reset_lds = e->P.lds.pre + (nblk + 2) * 4; }  // prefix behind every class's scratch
   e->lds_bytes = reset_lds;
@@ -267,11 +271,22 @@ static int finish_create(ge_engine *e, ge_engine **out) {
     if (hr != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the reset kernel"); }
   }
   // ---- quad-per-slot step kernel of the edge-action envs: its LDS stage (mask rows + node sets of 256 slots) passes 64 KB
-  if (!rg && (P.env_type == GE_STEINER_TREE || P.env_type == GE_MULTICAST_ROUTING) && ge_edge_fits(P.AW, P.W) && ge_edge_lds_bytes(P.AW, P.W) > 64 * 1024) {
-    const int bytes = (int)ge_edge_lds_bytes(P.AW, P.W);
-    if (P.env_type == GE_STEINER_TREE) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_STEINER_TREE, true>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_STEINER_TREE, false>), bytes); }
-    else { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_MULTICAST_ROUTING, true>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_MULTICAST_ROUTING, false>), bytes); }
+  if (edge_quad(e) && edge_lds(e) > 64 * 1024) {
+    const int bytes = (int)edge_lds(e);
+    if (P.env_type == GE_STEINER_TREE && rg) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_STEINER_TREE, true, true>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_STEINER_TREE, false, true>), bytes); }
+    else if (rg) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_MULTICAST_ROUTING, true, true>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_MULTICAST_ROUTING, false, true>), bytes); }
+    else if (P.env_type == GE_STEINER_TREE) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_STEINER_TREE, true, false>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_STEINER_TREE, false, false>), bytes); }
+    else { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_MULTICAST_ROUTING, true, false>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_MULTICAST_ROUTING, false, false>), bytes); }
     if (hr != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the edge step kernel"); }
+  }
+  // ---- multi-class engine, thread-per-slot step kernel: the LDS stage holds one node set of the widest class per slot
+  if (rg && (size_t)GE_STEP_BLOCK * P.W * 8 + GE_STEP_BLOCK + 64 > 64 * 1024) {
+    const int bytes = (int)((size_t)GE_STEP_BLOCK * P.W * 8 + GE_STEP_BLOCK + 64);
+    const bool pr = (P.env_type == GE_LONGEST_PATH || P.env_type == GE_TSP) && P.parenting >= 2;
+    if (pr && P.env_type == GE_TSP) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_TSP, true, true, 2>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_TSP, false, true, 2>), bytes); }
+    else if (pr) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_LONGEST_PATH, true, true, 2>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_LONGEST_PATH, false, true, 2>), bytes); }
+    else { GE_FOR_RAGGED_ENV(P.env_type, hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<ENV, true, true, 0>), bytes)); if (hr == hipSuccess) GE_FOR_RAGGED_ENV(P.env_type, hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<ENV, false, true, 0>), bytes)); }
+    if (hr != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the step kernel"); }
   }
   // ---- thread-per-slot step kernel: its LDS stage (one node set per slot of the workgroup) passes 64 KB above 2 048 nodes
   if (!rg && (size_t)GE_STEP_BLOCK * P.W * 8 + GE_STEP_BLOCK + 64 > 64 * 1024) {
@@ -317,7 +332,7 @@ extern "C" int ge_create(const ge_config *cfg, const ge_buffers *bufs, ge_engine
   e->P = P; e->cfg = *cfg; e->have_events = false;
   e->loaded = false; e->seeded = false; e->streams = false;
   e->spares = false; e->period = 0; e->swap_parts = 1; e->pending_calls = 0; memset(&e->RS, 0, sizeof(e->RS));
-  e->n_classes = 0; memset(&e->R, 0, sizeof(e->R));
+  e->n_classes = 0; memset(&e->R, 0, sizeof(e->R)); e->aw_max = P.AW;
   return finish_create(e, out);
 }
 
@@ -327,24 +342,23 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
                                 int32_t *slot_class, int32_t *class_start, ge_engine **out) {
   if (!cfgs || !bufs || !out || !class_table || !slot_class || !class_start || n_classes < 1) return fail(GE_E_BADARG, "null argument");
   const int t = cfgs[0].env_type;
-  if (t != GE_SHORTEST_PATH && t != GE_DENSEST_SUBGRAPH && t != GE_MAX_INDEPENDENT_SET)
-    return fail(GE_E_UNSUPPORTED, "the multi-class engine is built for ShortestPath, DensestSubgraph and MaxIndependentSet (BASELINE config 5)");
   int64_t total = 0;
   for (int c = 0; c < n_classes; c++) total += cfgs[c].num_envs;
-  if (cfgs[0].is_eval_env && t == GE_MAX_INDEPENDENT_SET && !cfgs[0].weighted)
-    return fail(GE_E_UNSUPPORTED, "is_eval_env of unweighted MaxIndependentSet (the clique-removal baseline, a launch per uniform engine) is not built for the multi-class engine");
   if (total > 8192 * GE_STEP_BLOCK) return fail(GE_E_TOOBIG, "num_envs > 2M per engine");
   ge_engine *e = new (std::nothrow) ge_engine();
   if (!e) return fail(GE_E_BADARG, "out of host memory");
   e->classes.resize(n_classes);
   std::vector<int32_t> start(n_classes + 1, 0), cls_of((size_t)total);
-  int wmin = 8, widest = 0;
+  int widest = 0, aw_max = 0;
   for (int c = 0; c < n_classes; c++) {
     GeParams &C = e->classes[c];
     int rc = derive(&cfgs[c], C, (int)total);
     if (rc == GE_OK) rc = check_buffers(C, &bufs[c]);
     if (rc == GE_OK && (cfgs[c].env_type != t || cfgs[c].autoreset != cfgs[0].autoreset || cfgs[c].seed_stride != cfgs[0].seed_stride))
       rc = fail(GE_E_BADARG, "the classes of a multi-class engine share env_type, autoreset and seed_stride");
+    if (rc == GE_OK && (cfgs[c].weighted != cfgs[0].weighted || cfgs[c].parenting != cfgs[0].parenting || cfgs[c].spatial != cfgs[0].spatial ||
+                        cfgs[c].is_eval_env != cfgs[0].is_eval_env))
+      rc = fail(GE_E_BADARG, "the classes of a multi-class engine share weighted, parenting, spatial and is_eval_env (they differ in n, m and the per-instance scalars only)");
     if (rc == GE_OK && (cfgs[c].env_index_base != cfgs[0].env_index_base + start[c] || bufs[c].seed != bufs[0].seed + start[c] ||
                         bufs[c].episode != bufs[0].episode + start[c] || bufs[c].mt_state != bufs[0].mt_state + (int64_t)start[c] * GE_SEED_DEPTH * 2 * GE_MT_N))
       rc = fail(GE_E_BADARG, "classes follow one another in slot order: env_index_base, seed, episode and mt_state of class c start at its first global slot");
@@ -357,8 +371,13 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
     start[c + 1] = start[c] + cfgs[c].num_envs;
     for (int i = start[c]; i < start[c + 1]; i++) cls_of[(size_t)i] = c;
     if (C.n > e->classes[widest].n) widest = c;
+    if (C.AW > aw_max) aw_max = C.AW;
   }
-  (void)wmin;
+  // parenting >= 2 of LongestPath / TSP: one PRUNE form for the whole engine -- the walks in memory (PRUNE 2) as soon as one class is
+  // above GE_MAXW words, and then every class needs its prune_scratch (ge_layout reports none for a class that would fit registers)
+  if ((t == GE_LONGEST_PATH || t == GE_TSP) && cfgs[0].parenting >= 2 && e->classes[widest].W > GE_MAXW)
+    for (int c = 0; c < n_classes; c++)
+      if (!bufs[c].prune_scratch) { delete e; return fail(GE_E_BADARG, "parenting >= 2 with a class above 512 nodes runs the residual-graph walks in memory for every class: each class needs prune_scratch ([B_c, 4, W_c] uint64)"); }
   // one launch geometry of the generic feature kernel per LDS bucket: the wave count every class of the bucket can hold -- two
   // workgroups per CU where that leaves at least four waves, else one
   memset(e->bk, 0, sizeof(e->bk));
@@ -377,12 +396,18 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
         if (pass == 0) ge_make_ldsf(C, (int)total); else ge_make_ldsf(C, (int)total, 0, 160 * 1024 - 2048);
         ge_tune_feat_parts(C);
         if (C.lds.total > K.reset_lds) K.reset_lds = C.lds.total;
-        if (C.n > 64) { anygen = true; if (C.ldsf.total > K.gen_lds) K.gen_lds = C.ldsf.total; if (C.ldsf.waves > waves) waves = C.ldsf.waves; }
+        if (C.n > 64 || C.spatial) { anygen = true; if (C.ldsf.total > K.gen_lds) K.gen_lds = C.ldsf.total; if (C.ldsf.waves > waves) waves = C.ldsf.waves; }  // (spatial TSP: no n <= 64 fast path)
       }
       if (2 * (K.gen_lds + (nblk_all + 2) * 4) <= kMaxLds) break;  // two workgroups per CU: the classes keep their own choice
     }
     K.used = any; K.gen_used = anygen; K.gen_waves = waves;
     if (!any) continue;
+    if (!anygen) {  // one wave per slot (ge_make_ldsf: n <= 64), sized for the bucket's largest class
+      int fb = 0;
+      for (const GeParams &C : e->classes) if (C.bucket == b && C.ldsf.total > fb) fb = C.ldsf.total;
+      K.fb_pre_off = ge_align16(fb); K.fb_lds = K.fb_pre_off + (nblk_all + 2) * 4;
+      if (K.fb_lds > 64 * 1024 && GE_SET_MAX_DYN_LDS(ge_k_features<true>, K.fb_lds) != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the feature kernel"); }
+    }
     if (K.reset_lds < GE_SEED_LDS_BYTES) K.reset_lds = GE_SEED_LDS_BYTES;
     { int per = kMaxLds / K.reset_lds; if (per > 16) per = 16; if (per < 1) per = 1; K.reset_grid = 256 * per; if (K.reset_grid > total) K.reset_grid = (int)total; }
     if (anygen) {
@@ -400,12 +425,16 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
   e->have_events = false; e->loaded = false; e->seeded = false; e->streams = false;
   e->spares = false; e->period = 0; e->swap_parts = 1; e->pending_calls = 0; memset(&e->RS, 0, sizeof(e->RS));
   e->n_classes = n_classes;
+  e->aw_max = aw_max;
+  e->P.AW = aw_max;  // (the edge step kernel's LDS stage: the widest mask row, which for the edge-action envs need not be the widest class's)
   if (hipMemcpy(class_table, e->classes.data(), sizeof(GeParams) * (size_t)n_classes, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(slot_class, cls_of.data(), sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(class_start, start.data(), sizeof(int32_t) * (size_t)(n_classes + 1), hipMemcpyHostToDevice) != hipSuccess) {
     delete e; return fail(GE_E_LAUNCH, "cannot copy the class table to the device");
   }
   e->R.classes = (const GeParams *)class_table; e->R.slot_class = slot_class; e->R.class_start = class_start; e->R.n_classes = n_classes;
+  e->R.f64_tsp_e = 0;
+  for (const GeParams &C : e->classes) if (C.env_type == GE_TSP && C.n <= 64 && C.E > e->R.f64_tsp_e) e->R.f64_tsp_e = C.E;
   return finish_create(e, out);
 }
 
@@ -525,9 +554,14 @@ static int launch_features(ge_engine *e, const GeParams &V, const GeRagged &VR, 
     if (rc != GE_OK) return rc;
     // the fast path's fallback list (normally empty); multi-class engine: every slot of a class with n > 64, feat_parts workgroups each
     if (rg) {
-      for (int b = 0; b < GE_MAX_BUCKETS && rc == GE_OK; b++) {  // one launch per LDS bucket that has classes with n > 64
+      for (int b = 0; b < GE_MAX_BUCKETS && rc == GE_OK; b++) {  // one launch per LDS bucket
         const GeBucket &K = e->bk[b];
-        if (!K.gen_used) continue;
+        if (!K.used) continue;
+        if (!K.gen_used) {  // classes with n <= 64 only: the list holds the rare slots too deep for the fast path (eight workgroups, as in a uniform engine)
+          GE_LAUNCH(ge_k_features<true>, 8, GE_WAVE, K.fb_lds, stream, V, VR, as_list(run), K.fb_pre_off, b);
+          rc = check_launch("feature kernel (fallback list)");
+          continue;
+        }
         int64_t want = (int64_t)K.gen_grid * ge_feat_workgroups(V.feat_parts) * (queue ? 1 : 4);
         if (small && want > 288) want = 288;
         if (want > 65535 * 16) want = 65535 * 16;
@@ -560,29 +594,34 @@ static int launch_features(ge_engine *e, const GeParams &V, const GeRagged &VR, 
   return launch_combine(e, V, VR, run, small, stream);
 }
 
-// is_eval_env baselines that are sequential programs (ge_tsp_eval.h: TSP Christofides, MaxIndependentSet clique removal) for the
-// regenerated slots, on the slabs the graph kernel wrote
-static int launch_seq_baseline(ge_engine *e, const GeParams &P, int queue, void *stream) {
-  const uint64_t slot_bytes = eval_slot_bytes(P);
+// is_eval_env baselines that are sequential programs (ge_tsp_eval.h: TSP Christofides, MaxIndependentSet clique removal, SteinerTree
+// Kou) for the regenerated slots, on the slabs the graph kernel wrote.  Multi-class engine: one launch over all slots; every item
+// finds its class and runs on that class's eval_scratch (VR: the live or the spare class table)
+static int launch_seq_baseline(ge_engine *e, const GeParams &P, const GeRagged &VR, int queue, void *stream) {
+  const bool rg = e->n_classes > 0;
+  const uint64_t slot_bytes = rg ? 0 : eval_slot_bytes(P);
   const int nblk = (P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK;
-  (void)e;
   if (P.env_type == GE_MAX_INDEPENDENT_SET) {
     int g = (P.B + GE_TSP_EVAL_THREADS - 1) / GE_TSP_EVAL_THREADS; if (g > 4096) g = 4096;
-    GE_LAUNCH(ge_k_mis_baseline, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+    if (rg) GE_LAUNCH(ge_k_mis_baseline<true>, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+    else GE_LAUNCH(ge_k_mis_baseline<false>, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
     return check_launch("MaxIndependentSet baseline kernel");
   }
   if (P.env_type == GE_STEINER_TREE) {
     int g = (P.B + GE_TSP_EVAL_THREADS - 1) / GE_TSP_EVAL_THREADS; if (g > 4096) g = 4096;
-    GE_LAUNCH(ge_k_steiner_baseline, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+    if (rg) GE_LAUNCH(ge_k_steiner_baseline<true>, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+    else GE_LAUNCH(ge_k_steiner_baseline<false>, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
     return check_launch("SteinerTree baseline kernel");
   }
-  const int pre_off = GE_WAVE * P.W * 8;
+  const int pre_off = GE_WAVE * P.W * 8;  // (P.W: the widest class's in a multi-class engine)
   int grid = P.B < 2048 ? P.B : 2048;
-  GE_LAUNCH(ge_k_tsp_closure, grid, GE_TSP_EVAL_THREADS, pre_off + (nblk + 2) * 4, stream, P, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes, pre_off);
+  if (rg) GE_LAUNCH(ge_k_tsp_closure<true>, grid, GE_TSP_EVAL_THREADS, pre_off + (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes, pre_off);
+  else GE_LAUNCH(ge_k_tsp_closure<false>, grid, GE_TSP_EVAL_THREADS, pre_off + (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes, pre_off);
   int rc = check_launch("TSP baseline: closure kernel");
   if (rc != GE_OK) return rc;
   grid = (P.B + GE_TSP_EVAL_THREADS - 1) / GE_TSP_EVAL_THREADS; if (grid > 4096) grid = 4096;
-  GE_LAUNCH(ge_k_tsp_tour, grid, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+  if (rg) GE_LAUNCH(ge_k_tsp_tour<true>, grid, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+  else GE_LAUNCH(ge_k_tsp_tour<false>, grid, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
   return check_launch("TSP baseline: tour kernel");
 }
 
@@ -626,7 +665,9 @@ static int launch_reset(ge_engine *e, const GeParams &V, const GeRagged &VR, con
   } else GE_FOR_ENV(V.env_type, GE_LAUNCH((ge_k_reset<ENV, false>), grid, GE_RESET_THREADS, e->lds_bytes, stream, V, VR, seeds, run, inj, nseed, -1));
   if (rc == GE_OK) rc = check_launch("reset kernel");
   if (rc != GE_OK) return rc;
-  if (!run.inject && e->n_classes == 0 && eval_slot_bytes(V)) rc = launch_seq_baseline(e, V, queue ? 1 : 0, stream);
+  bool baseline = eval_slot_bytes(V) != 0;
+  for (const GeParams &C : e->classes) baseline = baseline || eval_slot_bytes(C) != 0;  // (SteinerTree: Kou depends on the class's n_dests)
+  if (!run.inject && baseline) rc = launch_seq_baseline(e, V, VR, queue ? 1 : 0, stream);
   if (rc != GE_OK) return rc;
   if (!run.inject) rc = launch_features(e, V, VR, run, small, stream);
   if (rc == GE_OK && run.restart) e->seeded = true;
@@ -705,15 +746,26 @@ static size_t step_lds(const ge_engine *e) { return (size_t)GE_STEP_BLOCK * e->P
 
 extern "C" int ge_sample_actions(ge_engine *e, uint64_t policy_seed, int64_t *actions, void *stream);
 
-// parenting >= 2 of LongestPath / TSP: the instantiation of the step kernel that carries the residual-graph walks
+// parenting >= 2 of LongestPath / TSP: the instantiation of the step kernel that carries the residual-graph walks (multi-class
+// engine: PRUNE 1 when every class fits GE_MAXW words, else PRUNE 2 for all of them -- e->P.W is the widest class's)
 static bool prunes(const ge_engine *e) { return (e->P.env_type == GE_LONGEST_PATH || e->P.env_type == GE_TSP) && e->P.parenting >= 2; }
+#define GE_LAUNCH_STEP_RAGGED(SAMPLE, actions_arg, seed_arg)                                                                            \
+  do {                                                                                                                                  \
+    if (edge_quad(e) && e->P.env_type == GE_STEINER_TREE) GE_LAUNCH((ge_k_step_edge<GE_STEINER_TREE, SAMPLE, true>), grid, GE_EDGE_THREADS, edge_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
+    else if (edge_quad(e)) GE_LAUNCH((ge_k_step_edge<GE_MULTICAST_ROUTING, SAMPLE, true>), grid, GE_EDGE_THREADS, edge_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
+    else if (prunes(e) && e->P.env_type == GE_TSP && e->P.W > GE_MAXW) GE_LAUNCH((ge_k_step<GE_TSP, SAMPLE, true, 2>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
+    else if (prunes(e) && e->P.W > GE_MAXW) GE_LAUNCH((ge_k_step<GE_LONGEST_PATH, SAMPLE, true, 2>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
+    else if (prunes(e) && e->P.env_type == GE_TSP) GE_LAUNCH((ge_k_step<GE_TSP, SAMPLE, true, 1>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
+    else if (prunes(e)) GE_LAUNCH((ge_k_step<GE_LONGEST_PATH, SAMPLE, true, 1>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
+    else GE_FOR_RAGGED_ENV(e->P.env_type, GE_LAUNCH((ge_k_step<ENV, SAMPLE, true, 0>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg)); \
+  } while (0)
 #define GE_LAUNCH_STEP(SAMPLE, actions_arg, seed_arg)                                                                                   \
   do {                                                                                                                                  \
-    if (e->n_classes > 0) GE_FOR_RAGGED_ENV(e->P.env_type, GE_LAUNCH((ge_k_step<ENV, SAMPLE, true, 0>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg)); \
+    if (e->n_classes > 0) GE_LAUNCH_STEP_RAGGED(SAMPLE, actions_arg, seed_arg);                                                         \
     else if (path64(e) && e->spares) GE_LAUNCH((ge_k_step_path64<SAMPLE, true>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, actions_arg, seed_arg);  \
     else if (path64(e)) GE_LAUNCH((ge_k_step_path64<SAMPLE, false>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, actions_arg, seed_arg);  \
-    else if (edge_quad(e) && e->P.env_type == GE_STEINER_TREE) GE_LAUNCH((ge_k_step_edge<GE_STEINER_TREE, SAMPLE>), grid, GE_EDGE_THREADS, ge_edge_lds_bytes(e->P.AW, e->P.W), stream, e->P, actions_arg, seed_arg); \
-    else if (edge_quad(e)) GE_LAUNCH((ge_k_step_edge<GE_MULTICAST_ROUTING, SAMPLE>), grid, GE_EDGE_THREADS, ge_edge_lds_bytes(e->P.AW, e->P.W), stream, e->P, actions_arg, seed_arg); \
+    else if (edge_quad(e) && e->P.env_type == GE_STEINER_TREE) GE_LAUNCH((ge_k_step_edge<GE_STEINER_TREE, SAMPLE, false>), grid, GE_EDGE_THREADS, edge_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
+    else if (edge_quad(e)) GE_LAUNCH((ge_k_step_edge<GE_MULTICAST_ROUTING, SAMPLE, false>), grid, GE_EDGE_THREADS, edge_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
     else if (prunes(e) && e->P.env_type == GE_TSP && e->P.W > GE_MAXW) GE_LAUNCH((ge_k_step<GE_TSP, SAMPLE, false, 2>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
     else if (prunes(e) && e->P.W > GE_MAXW) GE_LAUNCH((ge_k_step<GE_LONGEST_PATH, SAMPLE, false, 2>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
     else if (prunes(e) && e->P.env_type == GE_TSP) GE_LAUNCH((ge_k_step<GE_TSP, SAMPLE, false, 1>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
@@ -723,14 +775,25 @@ static bool prunes(const ge_engine *e) { return (e->P.env_type == GE_LONGEST_PAT
 
 static bool path64(const ge_engine *e);
 static size_t step_lds(const ge_engine *e);
-// SteinerTree / MulticastRouting whose mask rows fit the LDS stage of the quad-per-slot kernel (ge_step.h, ge_k_step_edge)
+// SteinerTree / MulticastRouting whose mask rows fit the LDS stage of the quad-per-slot kernel (ge_step.h, ge_k_step_edge); a
+// multi-class engine stages every row with the stride of its widest class (e->aw_max) and node sets of its widest class (e->P.W)
 static bool edge_quad(const ge_engine *e) {
   static const bool off = getenv("GE_NO_EDGE_QUAD") != nullptr;  // diagnostic: the thread-per-slot kernel (before / after measurements)
-  return !off && e->n_classes == 0 && (e->P.env_type == GE_STEINER_TREE || e->P.env_type == GE_MULTICAST_ROUTING) && ge_edge_fits(e->P.AW, e->P.W);
+  return !off && (e->P.env_type == GE_STEINER_TREE || e->P.env_type == GE_MULTICAST_ROUTING) && ge_edge_fits(e->aw_max, e->P.W);
 }
+// (+ the class of every slot of the workgroup in a multi-class engine)
+static size_t edge_lds(const ge_engine *e) { return ge_edge_lds_bytes(e->aw_max, e->P.W) + (e->n_classes > 0 ? GE_EDGE_CLASS_BYTES : 0); }
 
 static bool path64(const ge_engine *e) {
   return e->n_classes == 0 && (e->P.env_type == GE_SHORTEST_PATH || e->P.env_type == GE_LONGEST_PATH) && e->P.W == 1 && e->P.parenting < 2;
+}
+
+// DistributionCenter with n <= 64 (in a multi-class engine: in any class) computes a centre's coverage range when it is chosen
+static bool dc_range(const ge_engine *e) {
+  if (e->P.env_type != GE_DISTRIBUTION_CENTER) return false;
+  if (e->n_classes == 0) return e->P.n <= 64;
+  for (const GeParams &C : e->classes) if (C.n <= 64) return true;
+  return false;
 }
 
 // call-order guard (the reference raises in the same situations): stepping needs an episode in the slots, and autoreset needs a
@@ -745,8 +808,9 @@ extern "C" int ge_step_only(ge_engine *e, const int64_t *actions, void *stream) 
   if (!e || !actions) return fail(GE_E_BADARG, "null argument");
   int rc = check_state(e);
   if (rc != GE_OK) return rc;
-  if (e->P.env_type == GE_DISTRIBUTION_CENTER && e->P.n <= 64) {  // the chosen centres' coverage ranges, computed when they are chosen
-    GE_LAUNCH(ge_k_dc_range, (e->P.B + GE_WAVE - 1) / GE_WAVE, GE_WAVE, (size_t)e->P.n * GE_WAVE * 8 + GE_WAVE * 64, stream, e->P, actions);
+  if (dc_range(e)) {  // the chosen centres' coverage ranges, computed when they are chosen
+    if (e->n_classes > 0) GE_LAUNCH(ge_k_dc_range<true>, (e->P.B + GE_WAVE - 1) / GE_WAVE, GE_WAVE, (size_t)64 * GE_WAVE * 8 + GE_WAVE * 64, stream, e->P, e->R, actions);
+    else GE_LAUNCH(ge_k_dc_range<false>, (e->P.B + GE_WAVE - 1) / GE_WAVE, GE_WAVE, (size_t)e->P.n * GE_WAVE * 8 + GE_WAVE * 64, stream, e->P, e->R, actions);
     rc = check_launch("coverage range kernel");
     if (rc != GE_OK) return rc;
   }
@@ -760,7 +824,7 @@ extern "C" int ge_step_only(ge_engine *e, const int64_t *actions, void *stream) 
 static int sample_and_step(ge_engine *e, uint64_t policy_seed, int64_t *scratch, void *stream) {
   int rc = check_state(e);
   if (rc != GE_OK) return rc;
-  if (e->P.env_type == GE_DISTRIBUTION_CENTER && e->P.n <= 64) {  // the coverage range kernel sits between the policy and the step
+  if (dc_range(e)) {  // the coverage range kernel sits between the policy and the step
     if (!scratch) return fail(GE_E_BADARG, "this env type needs actions_scratch");
     rc = ge_sample_actions(e, policy_seed, scratch, stream);
     return rc == GE_OK ? ge_step_only(e, scratch, stream) : rc;
@@ -904,7 +968,7 @@ extern "C" int ge_timed_empty_burst(ge_engine *e, int32_t k, void *stream, doubl
   const int grid = (e->P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK;
   const bool quad = edge_quad(e);
   (void)hipEventRecord(e->ev[0], st);
-  for (int j = 0; j < k; j++) GE_LAUNCH(ge_k_empty, grid, quad ? GE_EDGE_THREADS : GE_STEP_BLOCK, quad ? ge_edge_lds_bytes(e->P.AW, e->P.W) : step_lds(e), stream, 0);
+  for (int j = 0; j < k; j++) GE_LAUNCH(ge_k_empty, grid, quad ? GE_EDGE_THREADS : GE_STEP_BLOCK, quad ? edge_lds(e) : step_lds(e), stream, 0);
   (void)hipEventRecord(e->ev[1], st);
   if (hipEventSynchronize(e->ev[1]) != hipSuccess) return fail(GE_E_LAUNCH, "hipEventSynchronize failed");
   float ms = 0.f;

@@ -854,7 +854,7 @@ GE_F64_KERNEL ge_k_features64(GeParams P, GeRagged R, GeRun run, int tail_off) {
           if constexpr (RAGGED) {
             const int cls = ge_slot_class(R, env);
             const GeParams &C = R.classes[cls];
-            if (C.n <= 64) ge_f64_node_env(C, env - R.class_start[cls], ge_dyn_smem() + wv * ge_f64_node_wave_bytes(C.E, 0), lane);
+            if (C.n <= 64) ge_f64_node_env(C, env - R.class_start[cls], ge_dyn_smem() + wv * ge_f64_node_wave_bytes(R.f64_tsp_e, C.env_type == GE_TSP), lane);
           } else {
             ge_f64_node_env(P, env, ge_dyn_smem() + wv * ge_f64_node_wave_bytes(P.E, P.env_type == GE_TSP), lane);
           }

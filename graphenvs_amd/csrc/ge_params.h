@@ -115,6 +115,8 @@ struct GeRagged {
   const int32_t *slot_class;   // [B_total]
   const int32_t *class_start;  // [n_classes + 1] first global slot of every class
   int32_t n_classes;
+  int32_t f64_tsp_e;           // TSP: the most directed edges of a class with n <= 64 (the n <= 64 feature kernel's per-wave node area
+                               // holds the slot's weight codes: one stride for every wave of a workgroup, whichever class it runs)
 };
 
 static inline int ge_align16(int v) { return (v + 15) & ~15; }

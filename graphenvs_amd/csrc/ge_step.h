@@ -664,11 +664,16 @@ GE_KERNEL ge_k_step(GeParams PG, GeRagged R, const int64_t *actions, uint64_t po
 //    outside the tree; the reverse edge u -> v was open iff u is inside: only those are touched).
 // Replaces step() / _get_mask() of steiner_tree.py:116-157 and multicast_routing.py:155-266 for graphs whose rows fit the LDS stage
 // (ge_edge_fits); larger ones keep the thread-per-slot kernel above.
+// RAGGED (multi-class engine): PG is the engine-wide block (B = all slots, the reset queue; AW_max / W: the widest class's) and a
+// workgroup's 256 slots may straddle classes of different AW / W.  Every row is staged with the stride of the widest row and every
+// node set with the widest W; the stage looks up the class of each slot once (LDS table), a quad then runs its class's transition
+// on the class-local slot, through the class's buffers and A / AW / W.
 #define GE_EDGE_LPS 4
 #define GE_EDGE_THREADS (GE_STEP_BLOCK * GE_EDGE_LPS)
 GE_HOSTDEV int ge_edge_row_stride(int AW) { return AW + 4; }  // + 32 bytes: the quads of a wave start their rows in different banks
 GE_HOSTDEV size_t ge_edge_lds_bytes(int AW, int W) { return (size_t)GE_STEP_BLOCK * (size_t)(ge_edge_row_stride(AW) + W) * 8 + 2 * (GE_EDGE_THREADS / 64) * 4 + 64; }
 GE_HOSTDEV bool ge_edge_fits(int AW, int W) { return AW <= 32 && ge_edge_lds_bytes(AW, W) <= 100 * 1024; }
+#define GE_EDGE_CLASS_BYTES (GE_STEP_BLOCK * 4)  // RAGGED: the class of every slot of the workgroup, behind the queue counters
 
 GE_DEV uint32_t ge_quad_or32(uint32_t v) { v |= ge_quad_xor1(v); v |= ge_quad_xor2(v); return v; }
 GE_DEV uint64_t ge_quad_or64(uint64_t v) { return (uint64_t)ge_quad_or32((uint32_t)v) | ((uint64_t)ge_quad_or32((uint32_t)(v >> 32)) << 32); }
@@ -679,24 +684,49 @@ GE_DEV void ge_edge_writeback(uint64_t *dst, const uint64_t *row, uint32_t dirty
   for (uint32_t m = dirty; m; m &= m - 1, idx++) if ((idx & (GE_EDGE_LPS - 1)) == q) { const int w = (int)__builtin_ctz(m); dst[w] = row[w]; }
 }
 
-template <int ENV, bool SAMPLE>
-GE_KERNEL_LB(GE_EDGE_THREADS, 1) ge_k_step_edge(GeParams P, const int64_t *actions, uint64_t policy_seed) {
+template <int ENV, bool SAMPLE, bool RAGGED>
+GE_KERNEL_LB(GE_EDGE_THREADS, 1) ge_k_step_edge(GeParams PG, GeRagged R, const int64_t *actions, uint64_t policy_seed) {
   static_assert(ENV == GE_STEINER_TREE || ENV == GE_MULTICAST_ROUTING, "edge-action envs");
-  const ge_buffers &G = P.buf;
   const int tid = ge_tid(), q = tid & (GE_EDGE_LPS - 1);
-  const int i0 = ge_bid() * GE_STEP_BLOCK, sl = tid >> 2, i = i0 + sl;  // slot of this quad
-  const int n = P.n, W = P.W, F = P.F, A = P.A, AW = P.AW, RS = ge_edge_row_stride(AW);
+  const int i0 = ge_bid() * GE_STEP_BLOCK, sl = tid >> 2, ig = i0 + sl;  // global slot of this quad
+  const int WS = PG.W, AWS = PG.AW;  // LDS stage geometry (RAGGED: the widest node set and the widest mask row over the classes)
+  const int RS = ge_edge_row_stride(AWS);
   uint64_t *rows = (uint64_t *)ge_dyn_smem();           // [256][RS] mask rows
-  uint64_t *nbs = rows + (size_t)GE_STEP_BLOCK * RS;    // [256][W] node sets (in tree / has the message)
-  int *wcnt = (int *)(nbs + (size_t)GE_STEP_BLOCK * W);
-  int nb = P.B - i0; if (nb > GE_STEP_BLOCK) nb = GE_STEP_BLOCK;
-  // ---- stage: the workgroup's mask rows and node sets are contiguous in HBM
-  for (int idx = tid; idx < nb * AW; idx += GE_EDGE_THREADS) { const int e = idx / AW, w = idx - e * AW; rows[e * RS + w] = G.mask_bits[(int64_t)i0 * AW + idx]; }
-  for (int idx = tid; idx < nb * W; idx += GE_EDGE_THREADS) nbs[idx] = G.node_bits[(int64_t)i0 * W + idx];
+  uint64_t *nbs = rows + (size_t)GE_STEP_BLOCK * RS;    // [256][WS] node sets (in tree / has the message)
+  int *wcnt = (int *)(nbs + (size_t)GE_STEP_BLOCK * WS);
+  int nb = PG.B - i0; if (nb > GE_STEP_BLOCK) nb = GE_STEP_BLOCK;
+  int cls = 0, lo = 0;
+  if constexpr (RAGGED) {
+    int *scls = (int *)((uint8_t *)wcnt + 2 * (GE_EDGE_THREADS / 64) * 4 + 64);  // [256] class of every slot of the workgroup
+    for (int e = tid; e < nb; e += GE_EDGE_THREADS) scls[e] = R.slot_class[i0 + e];
+    ge_sync();
+    // ---- stage: a class's rows are contiguous in HBM; each element finds its slot's class in LDS
+    for (int idx = tid; idx < nb * AWS; idx += GE_EDGE_THREADS) {
+      const int e = idx / AWS, w = idx - e * AWS;
+      const GeParams &C = R.classes[scls[e]];
+      if (w < C.AW) rows[e * RS + w] = C.buf.mask_bits[(int64_t)(i0 + e - R.class_start[scls[e]]) * C.AW + w];
+    }
+    for (int idx = tid; idx < nb * WS; idx += GE_EDGE_THREADS) {
+      const int e = idx / WS, w = idx - e * WS;
+      const GeParams &C = R.classes[scls[e]];
+      if (w < C.W) nbs[idx] = C.buf.node_bits[(int64_t)(i0 + e - R.class_start[scls[e]]) * C.W + w];
+    }
+    if (sl < nb) { cls = scls[sl]; lo = R.class_start[cls]; }
+  } else {
+    // ---- stage: the workgroup's mask rows and node sets are contiguous in HBM
+    const ge_buffers &G = PG.buf;
+    const int AW = PG.AW, W = PG.W;
+    for (int idx = tid; idx < nb * AW; idx += GE_EDGE_THREADS) { const int e = idx / AW, w = idx - e * AW; rows[e * RS + w] = G.mask_bits[(int64_t)i0 * AW + idx]; }
+    for (int idx = tid; idx < nb * W; idx += GE_EDGE_THREADS) nbs[idx] = G.node_bits[(int64_t)i0 * W + idx];
+  }
   ge_sync();
-  uint64_t *row = rows + sl * RS, *nbits = nbs + sl * W;
+  const GeParams &P = RAGGED ? R.classes[cls] : PG;
+  const ge_buffers &G = P.buf;
+  const int i = ig - lo;  // slot inside its class (== ig in a uniform engine)
+  const int n = P.n, W = P.W, F = P.F, A = P.A, AW = P.AW;
+  uint64_t *row = rows + sl * RS, *nbits = nbs + sl * WS;
   bool want_reset = false, want_swap = false;
-  if (i < P.B) {
+  if (ig < PG.B) {
     const int64_t nbase = (int64_t)i * n, ebase = (int64_t)i * P.E;
     const ulonglong2 rec = ((const ulonglong2 *)G.slot_rec)[i];
     ge_quad_sync();  // the four lanes have read the record before lane 0 may rewrite it (lockstep on the GPU; the CPU harness runs lanes one after another)
@@ -734,9 +764,9 @@ GE_KERNEL_LB(GE_EDGE_THREADS, 1) ge_k_step_edge(GeParams P, const int64_t *actio
         const uint64_t gb = ge_quad_gather16(bit);
         a64 = (int64_t)(4 * jsel + qsel) * 64 + (int64_t)((gb >> (16 * qsel)) & 0xffffu);
       }
-      if (q == 0 && G.actions_out) G.actions_out[i] = a64;
+      if (q == 0 && PG.buf.actions_out) PG.buf.actions_out[ig] = a64;
     } else {
-      a64 = actions[i];
+      a64 = actions[ig];
     }
     double cost = ge_u64_as_f64(rec.x);
     double reward = 0.0; int done = 0, solved = -1, invalid = 0; bool acted = false, cost_hidden = false;
@@ -862,8 +892,8 @@ GE_KERNEL_LB(GE_EDGE_THREADS, 1) ge_k_step_edge(GeParams P, const int64_t *actio
           if (P.autoreset != 1) G.final_heur[i] = G.heuristic[i];
           if (P.autoreset) {
             want_reset = true;
-            want_swap = P.spare_state && P.spare_state[i];
-            if (want_swap) P.spare_state[i] = 0;
+            want_swap = PG.spare_state && PG.spare_state[ig];
+            if (want_swap) PG.spare_state[ig] = 0;
             st_out = 2;
           } else st_out = 1;
         }
@@ -871,7 +901,7 @@ GE_KERNEL_LB(GE_EDGE_THREADS, 1) ge_k_step_edge(GeParams P, const int64_t *actio
       if (acted || st == 3) ((ulonglong2 *)G.slot_rec)[i] = make_ulonglong2(ge_f64_as_u64(cost), ge_rec_make(ge_rec_head(rec.y), st_out, ge_rec_aux(rec.y), ts));
     }
   }
-  ge_enqueue_reset(P, wcnt, i0, i, tid, want_reset, want_swap);  // contains the barrier; only lane 0 of a quad ever wants
+  ge_enqueue_reset(PG, wcnt, i0, ig, tid, want_reset, want_swap);  // contains the barrier; global slot ids; only lane 0 of a quad ever wants
 }
 
 // Headline fast path: ShortestPath / LongestPath(parenting 0,1) with n <= 64.  One u64 per node set.  The kernel is
@@ -1019,12 +1049,20 @@ GE_KERNEL ge_k_step_path64(GeParams P, const int64_t *actions_in, uint64_t polic
 
 // DistributionCenter, n <= 64: the coverage range of the node each slot is about to choose, unless the row already exists
 // (a target's, or a node chosen earlier in the episode).  64-thread workgroups, one lane per slot, columns in LDS.
-GE_KERNEL ge_k_dc_range(GeParams P, const int64_t *actions) {
-  const int lane = ge_tid(), i = ge_bid() * GE_WAVE + lane, n = P.n;
+// RAGGED: PG is the engine-wide block; a slot of a class above 64 nodes has no range kernel (its rows are computed at reset), and
+// the LDS columns are sized for 64 nodes
+template <bool RAGGED>
+GE_KERNEL ge_k_dc_range(GeParams PG, GeRagged R, const int64_t *actions) {
+  const int lane = ge_tid(), ig = ge_bid() * GE_WAVE + lane;
   double *S = (double *)ge_dyn_smem();
-  uint8_t *stk = (uint8_t *)(S + n * GE_WAVE);
-  if (i >= P.B) return;
-  const int64_t a64 = actions[i];
+  uint8_t *stk = (uint8_t *)(S + (RAGGED ? 64 : PG.n) * GE_WAVE);
+  if (ig >= PG.B) return;
+  int cls = 0, lo = 0;
+  if constexpr (RAGGED) { cls = R.slot_class[ig]; lo = R.class_start[cls]; }
+  const GeParams &P = RAGGED ? R.classes[cls] : PG;
+  const int i = ig - lo, n = P.n;
+  if (RAGGED && n > 64) return;
+  const int64_t a64 = actions[ig];
   if (ge_rec_status(P.buf.slot_rec[2 * (int64_t)i + 1]) != 0 || a64 < 0 || a64 >= (int64_t)n) return;
   const int a = (int)a64;
   if (!((P.buf.mask_bits[i] >> a) & 1ull)) return;  // the step kernel will flag it invalid

@@ -38,16 +38,54 @@ GE_DEV int ge_tsp_count(const GeParams &P, int *pre, int queue) {
   return pre[(P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK];
 }
 
-GE_KERNEL ge_k_tsp_closure(GeParams P, int queue, uint8_t *scratch, uint64_t slot_bytes, int pre_off) {
-  uint64_t *done_all = (uint64_t *)ge_dyn_smem();  // [64 lanes][W] settled sets
+GE_HOSTDEV uint64_t ge_steiner_slot_bytes(int n, int m, int T) {
+  return ((((uint64_t)(2 * m + 1) * 2) + 15) & ~15ull) + ((((uint64_t)(2 * m + 1) * 8) + 15) & ~15ull) + ge_kou_arena_bytes(n, m, T);
+}
+
+// per-slot work space of the sequential is_eval_env baselines; 0 = none
+GE_HOSTDEV uint64_t eval_slot_bytes(const GeParams &P) {
+  if (!P.is_eval) return 0;
+  if (P.env_type == GE_TSP) return ge_ch_slot_bytes(P.n);
+  if (P.env_type == GE_MAX_INDEPENDENT_SET && !P.weighted) return ge_cr_slot_bytes(P.n, P.m);
+  if (P.env_type == GE_STEINER_TREE && P.n_dests > 1 && P.n_dests < P.n - 1) return ge_steiner_slot_bytes(P.n, P.m, P.T);  // steiner_tree.py:78-87: the Kou branch
+  return 0;
+}
+
+// RAGGED (multi-class engine): PG is the engine-wide block (all slots, the queue) and item `env` is a global slot; the baseline runs
+// on its class's slabs (local slot), its class's eval_scratch and per-slot size.  Returns false for a class without this baseline
+// (SteinerTree: n_dests outside the Kou branch).  Uniform engine: the launch's own block, scratch and size.
+template <bool RAGGED>
+GE_DEV bool ge_eval_item(const GeParams &PG, const GeRagged &R, int env, uint8_t *scratch, uint64_t slot_bytes, const GeParams *&P,
+                         int &local, uint8_t *&blk) {
+  if constexpr (RAGGED) {
+    const int cls = R.slot_class[env];
+    P = &R.classes[cls];
+    local = env - R.class_start[cls];
+    const uint64_t sb = eval_slot_bytes(*P);
+    blk = (uint8_t *)P->buf.eval_scratch + (uint64_t)local * sb;
+    return sb != 0;
+  } else {
+    (void)R;
+    P = &PG; local = env; blk = scratch + (uint64_t)env * slot_bytes;
+    return true;
+  }
+}
+
+template <bool RAGGED>
+GE_KERNEL ge_k_tsp_closure(GeParams PG, GeRagged R, int queue, uint8_t *scratch, uint64_t slot_bytes, int pre_off) {
+  uint64_t *done_all = (uint64_t *)ge_dyn_smem();  // [64 lanes][W] settled sets (W: the widest class's)
   int *pre = (int *)(ge_dyn_smem() + pre_off);
-  const int count = ge_tsp_count(P, pre, queue);
-  const int n = P.n, W = P.W, lane = ge_tid();
-  uint64_t *done = done_all + lane * W;
-  const ge_buffers &G = P.buf;
+  const int count = ge_tsp_count(PG, pre, queue);
+  const int lane = ge_tid();
+  uint64_t *done = done_all + lane * PG.W;
   for (int q = ge_bid(); q < count; q += ge_gdim()) {
-    const int env = queue ? ge_queue_slot(P, pre, q) : q;
-    int32_t *D = (int32_t *)(scratch + (uint64_t)env * slot_bytes);
+    const int genv = queue ? ge_queue_slot(PG, pre, q) : q;
+    const GeParams *Pp; int env; uint8_t *blk;
+    if (!ge_eval_item<RAGGED>(PG, R, genv, scratch, slot_bytes, Pp, env, blk)) continue;
+    const GeParams &P = *Pp;
+    const int n = P.n, W = P.W;
+    const ge_buffers &G = P.buf;
+    int32_t *D = (int32_t *)blk;
     const int32_t *rp = G.row_ptr + (int64_t)env * (n + 1);
     const int64_t ebase = (int64_t)env * P.E;
     for (int s = lane; s < n; s += GE_WAVE) {  // array Dijkstra from s: the row D[s][*] is the tentative-distance array
@@ -78,13 +116,16 @@ GE_KERNEL ge_k_tsp_closure(GeParams P, int queue, uint8_t *scratch, uint64_t slo
   }
 }
 
-GE_KERNEL ge_k_tsp_tour(GeParams P, int queue, uint8_t *scratch, uint64_t slot_bytes) {
+template <bool RAGGED>
+GE_KERNEL ge_k_tsp_tour(GeParams PG, GeRagged R, int queue, uint8_t *scratch, uint64_t slot_bytes) {
   int *pre = (int *)ge_dyn_smem();
-  const int count = ge_tsp_count(P, pre, queue);
-  const int n = P.n;
+  const int count = ge_tsp_count(PG, pre, queue);
   for (int q = ge_bid() * GE_TSP_EVAL_THREADS + ge_tid(); q < count; q += ge_gdim() * GE_TSP_EVAL_THREADS) {
-    const int env = queue ? ge_queue_slot(P, pre, q) : q;
-    uint8_t *blk = scratch + (uint64_t)env * slot_bytes;
+    const int genv = queue ? ge_queue_slot(PG, pre, q) : q;
+    const GeParams *Pp; int env; uint8_t *blk;
+    if (!ge_eval_item<RAGGED>(PG, R, genv, scratch, slot_bytes, Pp, env, blk)) continue;
+    const GeParams &P = *Pp;
+    const int n = P.n;
     ge_ch c;
     c.err = 0;
     ge_ch_carve(&c, blk + ge_ch_align((uint64_t)n * (uint64_t)n * 4u), n);
@@ -98,15 +139,19 @@ GE_KERNEL ge_k_tsp_tour(GeParams P, int queue, uint8_t *scratch, uint64_t slot_b
 // (max_independent_set.py:63-67), networkx's clique removal reproduced exactly (ge_clique_removal.h: dict orders of the graph
 // copies, CPython's set tables).  One LANE per regenerated slot on the slot's scratch block; replaces the min-degree greedy value
 // the graph kernel left in heuristic[] (which stays if the work space were ever too small).  Evaluation-time path, like the above.
-GE_KERNEL ge_k_mis_baseline(GeParams P, int queue, uint8_t *scratch, uint64_t slot_bytes) {
+template <bool RAGGED>
+GE_KERNEL ge_k_mis_baseline(GeParams PG, GeRagged R, int queue, uint8_t *scratch, uint64_t slot_bytes) {
   int *pre = (int *)ge_dyn_smem();
-  const int count = ge_tsp_count(P, pre, queue);
-  const int n = P.n;
-  const ge_buffers &G = P.buf;
+  const int count = ge_tsp_count(PG, pre, queue);
   for (int q = ge_bid() * GE_TSP_EVAL_THREADS + ge_tid(); q < count; q += ge_gdim() * GE_TSP_EVAL_THREADS) {
-    const int env = queue ? ge_queue_slot(P, pre, q) : q;
+    const int genv = queue ? ge_queue_slot(PG, pre, q) : q;
+    const GeParams *Pp; int env; uint8_t *blk;
+    if (!ge_eval_item<RAGGED>(PG, R, genv, scratch, slot_bytes, Pp, env, blk)) continue;
+    const GeParams &P = *Pp;
+    const int n = P.n;
+    const ge_buffers &G = P.buf;
     ge_cr_work w;
-    ge_cr_carve(&w, scratch + (uint64_t)env * slot_bytes, n, P.m);
+    ge_cr_carve(&w, blk, n, P.m);
     const int32_t *rp = G.row_ptr + (int64_t)env * (n + 1);
     const int64_t ebase = (int64_t)env * P.E;
     for (int v = 0; v <= n; v++) w.ga.off[v] = rp[v];
@@ -120,18 +165,18 @@ GE_KERNEL ge_k_mis_baseline(GeParams P, int queue, uint8_t *scratch, uint64_t sl
 // (steiner_tree.py:84-87), reproduced exactly (ge_kou_exact.h: heap-ordered Dijkstra paths, stable Kruskal order over subgraph
 // views, CPython's set tables for tuples and ints, float64 sum order).  One LANE per regenerated slot; replaces the own Kou-style
 // value the graph kernel left in heuristic[] (which stays if the work space were ever too small).
-GE_HOSTDEV uint64_t ge_steiner_slot_bytes(int n, int m, int T) {
-  return ((((uint64_t)(2 * m + 1) * 2) + 15) & ~15ull) + ((((uint64_t)(2 * m + 1) * 8) + 15) & ~15ull) + ge_kou_arena_bytes(n, m, T);
-}
 
-GE_KERNEL ge_k_steiner_baseline(GeParams P, int queue, uint8_t *scratch, uint64_t slot_bytes) {
+template <bool RAGGED>
+GE_KERNEL ge_k_steiner_baseline(GeParams PG, GeRagged R, int queue, uint8_t *scratch, uint64_t slot_bytes) {
   int *pre = (int *)ge_dyn_smem();
-  const int count = ge_tsp_count(P, pre, queue);
-  const int n = P.n;
-  const ge_buffers &G = P.buf;
+  const int count = ge_tsp_count(PG, pre, queue);
   for (int q = ge_bid() * GE_TSP_EVAL_THREADS + ge_tid(); q < count; q += ge_gdim() * GE_TSP_EVAL_THREADS) {
-    const int env = queue ? ge_queue_slot(P, pre, q) : q;
-    uint8_t *blk = scratch + (uint64_t)env * slot_bytes;
+    const int genv = queue ? ge_queue_slot(PG, pre, q) : q;
+    const GeParams *Pp; int env; uint8_t *blk;
+    if (!ge_eval_item<RAGGED>(PG, R, genv, scratch, slot_bytes, Pp, env, blk)) continue;
+    const GeParams &P = *Pp;
+    const int n = P.n;
+    const ge_buffers &G = P.buf;
     uint16_t *adj = (uint16_t *)blk;
     double *w = (double *)(blk + ((((uint64_t)(2 * P.m + 1) * 2) + 15) & ~15ull));
     const int64_t ebase = (int64_t)env * P.E;

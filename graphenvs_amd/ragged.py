@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .vector_env import GraphBatch, VectorGraphEnv
+from .vector_env import GraphBatch, VectorGraphEnv, normalize_kwargs
 
 # per-slot arrays kept engine-wide (class c owns rows [start_c, start_c + B_c))
 _GLOBAL = dict(seed=((), torch.int32), episode=((), torch.int64), mt_state=((_lib.SEED_DEPTH, 2, 624), torch.int32),
@@ -20,21 +20,42 @@ _GLOBAL = dict(seed=((), torch.int32), episode=((), torch.int64), mt_state=((_li
                final_cost=((), torch.float64), final_heur=((), torch.float64), final_len=((), torch.int32),
                counters=((2,), torch.int32))
 
+# constructor kwargs a size class may set for itself (the per-instance scalars: ge_config.n_dests / max_distance / n_choices); every
+# other kwarg is the same for all classes (ge_create_ragged refuses classes that differ in weighted, parenting, spatial or is_eval_env)
+CLASS_KWARGS = ("n_dests", "n_products", "max_distance", "target_count", "n_choices")
+
 
 class RaggedVectorEnv:
-    """One env id, several size classes: ``sizes = [(num_envs, n_nodes, n_edges), ...]``.  Slots are numbered class after class;
-    slot g runs seed (seed + g) like a uniform engine.  ``classes[c]`` are views of class c (``.mask`` [B_c, A_c], ``.t[...]``)."""
+    """One env id, several size classes: ``sizes = [(num_envs, n_nodes, n_edges), ...]``; an entry may carry a fourth element, a
+    dict of the class's own values of ``CLASS_KWARGS`` (e.g. MST: ``("SteinerTree-v0", [(b, n, m, dict(n_dests=n - 1)), ...])``).
+    ``n_edges = -1`` takes the reference's default where it has one.  Slots are numbered class after class; slot g runs seed
+    (seed + g) like a uniform engine.  ``classes[c]`` are views of class c (``.mask`` [B_c, A_c] -- A_c = 2 m_c for the edge-action
+    envs --, ``.t[...]``)."""
 
     def __init__(self, env_id, sizes, device="cuda", env_index_base=0, seed_stride=None, autoreset=True, _library=None, prefetch=None,
                  **kwargs):
         self.env_id, self.device = env_id, torch.device(device)
-        self.sizes = [(int(b), int(n), int(m)) for b, n, m in sizes]
+        # every class normalised like a uniform engine (the reference's asserts and defaults), before any device allocation
+        self.class_kwargs, self.sizes = [], []
+        for entry in sizes:
+            if len(entry) not in (3, 4):
+                raise TypeError(f"a sizes entry is (num_envs, n_nodes, n_edges[, kwargs]), got {entry!r}")
+            own = dict(entry[3]) if len(entry) == 4 else {}
+            bad = sorted(k for k in own if k not in CLASS_KWARGS)
+            if bad:
+                raise TypeError(f"{env_id}: per-class kwargs {bad} are not allowed (only {', '.join(CLASS_KWARGS)} may differ between classes)")
+            b, n = int(entry[0]), int(entry[1])
+            ckw = dict(kwargs, **own)
+            m = normalize_kwargs(env_id, n, int(entry[2]), **ckw)["n_edges"]
+            self.class_kwargs.append(ckw)
+            self.sizes.append((b, n, m))
         self.num_envs = B = sum(b for b, _, _ in self.sizes)
         stride = int(seed_stride) if seed_stride is not None else B
         self.seed_stride, self.env_index_base = stride, int(env_index_base)
         extra = dict(device=device, _library=_library) if _library is not None else dict(device=device)
-        probe = VectorGraphEnv(env_id, 1, self.sizes[0][1], self.sizes[0][2], _defer_create=True, **extra, **kwargs)
+        probe = VectorGraphEnv(env_id, 1, self.sizes[0][1], self.sizes[0][2], _defer_create=True, **extra, **self.class_kwargs[0])
         F, Fe, edge_env = probe.F, probe.Fe, env_id in ("SteinerTree-v0", "MulticastRouting-v0")
+        self.edge_env = edge_env
         self._L = probe._L
         dev = self.device
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
@@ -49,20 +70,27 @@ class RaggedVectorEnv:
         self.classes, self.slot_ptr, self._offsets = [], [0], []
         noff = eoff = slot = moff = 0
         ptr = [0]
-        for b, n, m in self.sizes:
+        for (b, n, m), ckw in zip(self.sizes, self.class_kwargs):
             E, A = 2 * m, A_of(n, m)
             views = dict(x=self.x[noff:noff + b * n], edge_index=self.edge_index[0, eoff:], edge_attr=self.edge_attr[eoff:eoff + b * E],
                          mask=self.mask_flat[moff:moff + b * A].view(b, A))
             views.update({k: self.g[k][slot:slot + b] for k in _GLOBAL})
             views.update({k: self.g[k] for k in ("reset_list", "reset_count", "work_list", "work_count")})
             env = VectorGraphEnv(env_id, b, n, m, env_index_base=self.env_index_base + slot, seed_stride=stride, autoreset=autoreset,
-                                 _views=views, node_id_base=noff, edge_row_stride=Ne, _defer_create=True, prefetch=0, **extra, **kwargs)
+                                 _views=views, node_id_base=noff, edge_row_stride=Ne, _defer_create=True, prefetch=0, **extra, **ckw)
             self.classes.append(env)
             self._offsets.append((noff, eoff, slot, moff, b, n, E, A))
             ptr += [noff + (i + 1) * n for i in range(b)]
             noff += b * n; eoff += b * E; slot += b; moff += b * A
             self.slot_ptr.append(slot)
         nc = len(self.classes)
+        # parenting >= 2 of LongestPath / TSP with a class above 512 nodes: the engine runs the residual-graph walks in memory for
+        # every class, so every class gets a prune_scratch ([B_c, 4, W_c] words), also those a uniform engine would keep in registers
+        if any(c.t["prune_scratch"] is not None for c in self.classes):
+            for c in self.classes:
+                if c.t["prune_scratch"] is None:
+                    dict.__setitem__(c.t, "prune_scratch", z((c.num_envs * 4 * c.W,), torch.int64))
+                    c.bufs = _lib.GeBuffers(**{k: (v.data_ptr() if v is not None else None) for k, v in dict.items(c.t)})
         self._table = torch.zeros(int(self._L.ge_ragged_table_bytes(nc)), dtype=torch.uint8, device=dev)
         self._slot_class, self._class_start = z((B,), torch.int32), z((nc + 1,), torch.int32)
         cfgs = (_lib.GeConfig * nc)(*[c.cfg for c in self.classes])
@@ -112,6 +140,15 @@ class RaggedVectorEnv:
 
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream) if self.device.type == "cuda" else C.c_void_p(0)
+
+    def edge_links(self):
+        """one [B_c, E_c, 2] tensor of local node ids per class (GraphInstance.edge_links of every slot of the class)"""
+        out = []
+        for noff, eoff, slot, moff, b, n, E, A in self._offsets:
+            ei = self.edge_index[:, eoff:eoff + b * E].view(2, b, E)
+            off = (torch.arange(b, device=self.device, dtype=torch.int64) * n + noff).view(1, -1, 1)
+            out.append((ei - off).permute(1, 2, 0).contiguous())
+        return out
 
     def graph(self):
         return GraphBatch(x=self.x, edge_index=self.edge_index, edge_attr=self.edge_attr, batch=self.batch, ptr=self.ptr,

@@ -184,11 +184,13 @@ int ge_get_layout(const ge_config *cfg, ge_layout *out);
 int ge_create(const ge_config *cfg, const ge_buffers *bufs, ge_engine **out);
 int ge_destroy(ge_engine *e);
 
-/* Multi-class ("ragged") engine -- BASELINE config 5: env instances of ONE id but different (n_nodes, n_edges) stepped by one launch
- * sequence.  Every reference instance has a fixed geometry (shortest_path.py:23-45, densest_subgraph.py:25-50,
+/* Multi-class ("ragged") engine -- BASELINE config 5 and size curricula: env instances of ONE id but different (n_nodes, n_edges)
+ * stepped by one launch sequence.  Every reference instance has a fixed geometry (shortest_path.py:23-45, densest_subgraph.py:25-50,
  * max_independent_set.py:25-38), so a ragged batch is a list of size classes; class c is described exactly like a uniform engine
  * (cfgs[c], bufs[c]) and owns slots [start_c, start_c + num_envs_c) of the global slot order, start_c = sum of the earlier classes:
- *  - cfgs[c].env_index_base = cfgs[0].env_index_base + start_c; env_type, autoreset, seed_stride equal in all classes;
+ *  - cfgs[c].env_index_base = cfgs[0].env_index_base + start_c; env_type, autoreset, seed_stride, weighted, parenting, spatial and
+ *    is_eval_env equal in all classes (GE_E_BADARG otherwise); n_nodes, n_edges and the per-instance scalars (n_dests -- also
+ *    target_count / n_products --, max_distance, n_choices, dt_min / dt_max) may differ: MST is SteinerTree with n_dests = n - 1;
  *  - seed, episode, mt_state are ENGINE-wide arrays in slot order (bufs[c].seed = bufs[0].seed + start_c, ...); reset_list,
  *    reset_count, work_list, work_count (and actions_out) are taken from bufs[0] and sized for all slots; callers normally make
  *    every per-slot array engine-wide the same way and let the classes share the observation slabs through node_id_base /
@@ -197,8 +199,10 @@ int ge_destroy(ge_engine *e);
  *    device buffers the engine fills once, here (a synchronous copy).
  * ge_reset / ge_step / ge_sample_actions / ge_random_rollout / ge_vectorize then take arrays over ALL slots (ge_vectorize: the classes'
  * flat vectors one class after the other).  Every kernel maps a slot to its class and runs the class's code path; classes with
- * n_nodes <= 64 use the fast feature kernel, the others the generic one, inside the same launch sequence.  Built for ShortestPath,
- * DensestSubgraph and MaxIndependentSet; ge_inject_state is not available. */
+ * n_nodes <= 64 use the fast feature kernel, the others the generic one, inside the same launch sequence.  Built for every env id,
+ * is_eval_env baselines included.  LongestPath / TSP with parenting >= 2: when a class has more than 512 nodes the residual-graph
+ * walks run in memory for EVERY class, and every class then needs prune_scratch ([num_envs_c, 4, W_c] uint64) even where
+ * ge_get_layout reports none for it.  ge_inject_state and ge_reset_continue are not available (GE_E_UNSUPPORTED). */
 int64_t ge_ragged_table_bytes(int32_t n_classes);
 int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, int32_t n_classes, void *class_table,
                      int32_t *slot_class, int32_t *class_start, ge_engine **out);
