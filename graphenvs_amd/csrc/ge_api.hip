@@ -29,36 +29,57 @@ struct GeBucket {
 };
 static int bucket_of(int n) { return n <= 128 ? 0 : (n <= 256 ? 1 : (n <= 512 ? 2 : 3)); }
 
+// The kernel instantiations an engine runs, chosen once when it is created (select_kernels).  Every launch and every raise of a
+// dynamic-LDS limit takes its kernel from here, so the instantiation whose limit was raised is the one that is launched.
+typedef void (*GeBaselineFn)(GeParams, GeRagged, int, uint8_t *, uint64_t);
+struct GeKernels {
+  void (*reset)(GeParams, GeRagged, const uint32_t *, GeRun, GeInject, int, int);
+  void (*features)(GeParams, GeRagged, GeRun, int, int);
+  void (*features64)(GeParams, GeRagged, GeRun, int);
+  void (*feat_combine)(GeParams, GeRagged, GeRun);
+  void (*swap)(GeParams, GeRagged, GeRagged, ge_buffers, int);
+  void (*sample)(GeParams, GeRagged, uint64_t, int64_t *);
+  void (*dc_range)(GeParams, GeRagged, const int64_t *);
+  void (*tsp_closure)(GeParams, GeRagged, int, uint8_t *, uint64_t, int);
+  GeBaselineFn tsp_tour, mis_baseline, steiner_baseline;
+  void (*step[2])(GeParams, GeRagged, const int64_t *, uint64_t);  // [SAMPLE]
+  int step_threads;
+  size_t step_lds;
+  bool step_quad;  // step[] is the quad-per-slot kernel of the edge-action envs (ge_k_step_edge)
+  void (*step_path64[2][2])(GeParams, const int64_t *, uint64_t);  // [SAMPLE][SPARES], set where it takes the place of step[] (path64)
+};
+
 struct ge_engine {
   GeParams P;
   ge_config cfg;
+  GeKernels k = {};
   int reset_grid;     // workgroups of the queue-mode reset launch
   int lds_bytes;
   int feat_lds, feat_grid, feat_fast, gen_grid, gen_lds;  // structural-feature kernel launch geometry
   hipEvent_t ev[4];
-  bool have_events;
+  bool have_events = false;
   int nseed;      // seeding workgroups at the head of the queue-mode reset launch (64 queued slots each)
   // multi-class ("ragged") engine: P is then the engine-wide block (B = all slots, global queue / seed / episode / mt_state arrays,
   // n / m / W = the widest class) and R names the device copy of the class table
-  int n_classes;
-  GeRagged R;
-  int aw_max;     // multi-class engine: the widest mask row over the classes (edge-action envs: 2 m words, not a function of n)
+  int n_classes = 0;
+  GeRagged R = {};
+  int aw_max;     // the widest mask row (multi-class engine: over the classes; edge-action envs: 2 m words, not a function of n)
   std::vector<GeParams> classes;  // host copy (ge_vectorize launches per class)
   int feat64_pre_off, gen_pre_off;
   int lds_bytes_inject;  // GeParams.nocolw engines: ge_inject_state runs the graph kernel on the full LDS carve (the injected rows need the list)
-  GeBucket bk[GE_MAX_BUCKETS];
-  bool loaded;    // the slots hold an episode (ge_reset or ge_inject_state ran)
-  bool seeded;    // the generator-state ring is valid (ge_reset, or ge_inject_state with seeds)
-  bool streams;   // stream_state holds the streams a regeneration left behind (ge_reset; a restored snapshot)
+  GeBucket bk[GE_MAX_BUCKETS] = {};
+  bool loaded = false;    // the slots hold an episode (ge_reset or ge_inject_state ran)
+  bool seeded = false;    // the generator-state ring is valid (ge_reset, or ge_inject_state with seeds)
+  bool streams = false;   // stream_state holds the streams a regeneration left behind (ge_reset; a restored snapshot)
   // episode prefetch (ge_attach_spares): PS is the engine seen through its spare image -- the same geometry, generator ring,
   // seed[] / episode[] and work lists, but every per-slot slab is the image's and the queue is the refill list
-  bool spares;
+  bool spares = false;
   GeParams PS;
-  GeRagged RS;                     // multi-class engine: class table whose bufs are the images
+  GeRagged RS = {};                // multi-class engine: class table whose bufs are the images
   std::vector<GeParams> classesS;  // its host copy
-  int period, swap_parts;
-  int64_t pending_calls;           // ge_reset_pending calls since the last refill
-  int32_t *refill_list, *refill_count;
+  int period = 0, swap_parts = 1;
+  int64_t pending_calls = 0;       // ge_reset_pending calls since the last refill
+  int32_t *refill_list = nullptr, *refill_count = nullptr;
 };
 
 // ---- what a reset-path launch does (GeRun, ge_params.h): the only places where a request becomes flags
@@ -84,6 +105,19 @@ static const char g_source_hash[] = "GE_SOURCE_HASH=" GE_SOURCE_HASH;  // the ma
 extern "C" const char *ge_source_hash(void) { return g_source_hash + 15; }
 
 static const int kMaxLds = 160 * 1024;
+static const GeInject kNoInject = {nullptr, nullptr, nullptr, nullptr, nullptr};
+static int step_blocks(int64_t B) { return (int)((B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK); }  // workgroups of GE_STEP_BLOCK slots (one queue counter each)
+// workgroups that stay resident at `lds` bytes each (256 CUs, at most 16 per CU), no more than one per slot
+static int resident_grid(int lds, int64_t B) {
+  int per_cu = kMaxLds / (lds > 0 ? lds : 1);
+  if (per_cu > 16) per_cu = 16;
+  if (per_cu < 1) per_cu = 1;
+  return 256 * per_cu > B ? (int)B : 256 * per_cu;
+}
+static int64_t obs_len(const GeParams &P) { return (int64_t)P.n * P.F + (int64_t)P.E * P.Fe + 2 * (int64_t)P.E; }  // flat observation of one slot
+// parenting >= 2 of LongestPath / TSP: the step kernel carries the residual-graph walks (PRUNE 1: node sets of up to GE_MAXW words
+// in registers; PRUNE 2: in prune_scratch)
+static bool prunes(const GeParams &P) { return (P.env_type == GE_LONGEST_PATH || P.env_type == GE_TSP) && P.parenting >= 2; }
 #ifndef GE_NP_EARLY_MAX
 #define GE_NP_EARLY_MAX 256  // graphs up to this size hold the n x n delay matrix in LDS (a test build lowers it to run the late path, ge_np_draws_edges, on small graphs)
 #endif
@@ -186,33 +220,15 @@ extern "C" int ge_get_layout(const ge_config *cfg, ge_layout *out) {
   if (!out) return fail(GE_E_BADARG, "null layout");
   out->F = P.F; out->Fe = P.Fe; out->A = P.A; out->W = P.W; out->E = P.E;
   out->total_nodes = (int64_t)P.B * P.n; out->total_edges = (int64_t)P.B * P.E;
-  out->obs_len = (int64_t)P.n * P.F + (int64_t)P.E * P.Fe + 2 * (int64_t)P.E;
+  out->obs_len = obs_len(P);
   out->reset_lds_bytes = P.lds.total;
   out->feat_parts = P.feat_parts;
   out->eval_scratch_bytes = (int64_t)((uint64_t)P.B * eval_slot_bytes(P));
-  out->prune_scratch_words = ((P.env_type == GE_LONGEST_PATH || P.env_type == GE_TSP) && P.parenting >= 2 && P.W > GE_MAXW) ? (int64_t)P.B * 4 * P.W : 0;
+  out->prune_scratch_words = (prunes(P) && P.W > GE_MAXW) ? (int64_t)P.B * 4 * P.W : 0;
   return GE_OK;
 }
 
 extern "C" int ge_destroy(ge_engine *e);
-
-// the multi-class engine is instantiated for every env id; each case is explicit (the config-5 ids -- ShortestPath, DensestSubgraph,
-// MaxIndependentSet -- keep the instantiations they had when they were the only ones)
-#define GE_FOR_RAGGED_ENV(env_type, stmt)                                                           \
-  do {                                                                                              \
-    switch (env_type) {                                                                             \
-      case GE_SHORTEST_PATH: { constexpr int ENV = GE_SHORTEST_PATH; stmt; break; }                   \
-      case GE_LONGEST_PATH: { constexpr int ENV = GE_LONGEST_PATH; stmt; break; }                     \
-      case GE_STEINER_TREE: { constexpr int ENV = GE_STEINER_TREE; stmt; break; }                     \
-      case GE_TSP: { constexpr int ENV = GE_TSP; stmt; break; }                                       \
-      case GE_DENSEST_SUBGRAPH: { constexpr int ENV = GE_DENSEST_SUBGRAPH; stmt; break; }             \
-      case GE_MULTICAST_ROUTING: { constexpr int ENV = GE_MULTICAST_ROUTING; stmt; break; }           \
-      case GE_DISTRIBUTION_CENTER: { constexpr int ENV = GE_DISTRIBUTION_CENTER; stmt; break; }       \
-      case GE_PERISHABLE_DELIVERY: { constexpr int ENV = GE_PERISHABLE_DELIVERY; stmt; break; }       \
-      case GE_MAX_INDEPENDENT_SET: { constexpr int ENV = GE_MAX_INDEPENDENT_SET; stmt; break; }       \
-      default: break;                                                                               \
-    }                                                                                               \
-  } while (0)
 
 static int check_buffers(const GeParams &P, const ge_buffers *bufs) {
   const void *need[] = {bufs->x, bufs->edge_index, bufs->edge_attr, bufs->row_ptr, bufs->colw, bufs->scode, bufs->adj_bits, bufs->slot_rec,
@@ -230,19 +246,76 @@ static int check_buffers(const GeParams &P, const ge_buffers *bufs) {
   if (P.spatial && !bufs->sw64) return fail(GE_E_BADARG, "spatial TSP needs sw64");
   if (eval_slot_bytes(P) && !bufs->eval_scratch) return fail(GE_E_BADARG, "is_eval_env of TSP / unweighted MaxIndependentSet / SteinerTree (1 < n_dests < n - 1) needs eval_scratch (ge_layout.eval_scratch_bytes)");
   if (P.W == 1 && !bufs->node_rec) return fail(GE_E_BADARG, "n_nodes <= 64 needs node_rec");
-  if ((P.env_type == GE_LONGEST_PATH || P.env_type == GE_TSP) && P.parenting >= 2 && P.W > GE_MAXW && !bufs->prune_scratch)
+  if (prunes(P) && P.W > GE_MAXW && !bufs->prune_scratch)
     return fail(GE_E_BADARG, "parenting >= 2 on more than 512 nodes needs prune_scratch ([B, 4, W] uint64)");
   return GE_OK;
 }
 
-static bool edge_quad(const ge_engine *e);
-static size_t edge_lds(const ge_engine *e);
+// SteinerTree / MulticastRouting whose mask rows fit the LDS stage of the quad-per-slot kernel (ge_step.h, ge_k_step_edge); a
+// multi-class engine stages every row with the stride of its widest class (e->aw_max) and node sets of its widest class (e->P.W)
+static bool edge_quad(const ge_engine *e) {
+  static const bool off = getenv("GE_NO_EDGE_QUAD") != nullptr;  // diagnostic: the thread-per-slot kernel (before / after measurements)
+  return !off && (e->P.env_type == GE_STEINER_TREE || e->P.env_type == GE_MULTICAST_ROUTING) && ge_edge_fits(e->aw_max, e->P.W);
+}
 
-// launch geometry and LDS limits from e->P (uniform engine) or from the class table (multi-class engine); deletes e on failure
+static bool path64(const ge_engine *e) {
+  return e->n_classes == 0 && (e->P.env_type == GE_SHORTEST_PATH || e->P.env_type == GE_LONGEST_PATH) && e->P.W == 1 && e->P.parenting < 2;
+}
+
+// The only place where an engine becomes kernel instantiations (e->P, e->n_classes and e->aw_max are final).  `if constexpr` keeps
+// the set of instantiations to the ones an engine can run: the library is one translation unit and every extra kernel costs build time.
+template <int ENV, bool RAGGED>
+static void select_kernels(ge_engine *e) {
+  GeKernels &k = e->k;
+  k.reset = ge_k_reset<ENV, RAGGED>;
+  k.features = ge_k_features<RAGGED>;
+  k.features64 = ge_k_features64<RAGGED>;
+  k.feat_combine = ge_k_feat_combine<RAGGED>;
+  k.swap = ge_k_swap<RAGGED>;
+  k.sample = ge_k_sample<RAGGED>;
+  k.dc_range = ge_k_dc_range<RAGGED>;
+  k.tsp_closure = ge_k_tsp_closure<RAGGED>;
+  k.tsp_tour = ge_k_tsp_tour<RAGGED>;
+  k.mis_baseline = ge_k_mis_baseline<RAGGED>;
+  k.steiner_baseline = ge_k_steiner_baseline<RAGGED>;
+  // thread-per-slot step kernel: the LDS stage holds one node set per slot of the workgroup (multi-class engine: of the widest class)
+  k.step[0] = ge_k_step<ENV, false, RAGGED, 0>; k.step[1] = ge_k_step<ENV, true, RAGGED, 0>;
+  k.step_threads = GE_STEP_BLOCK;
+  k.step_lds = (size_t)GE_STEP_BLOCK * e->P.W * 8 + GE_STEP_BLOCK + 64;
+  if constexpr (ENV == GE_STEINER_TREE || ENV == GE_MULTICAST_ROUTING) {
+    if (edge_quad(e)) {
+      k.step[0] = ge_k_step_edge<ENV, false, RAGGED>; k.step[1] = ge_k_step_edge<ENV, true, RAGGED>;
+      k.step_quad = true;
+      k.step_threads = GE_EDGE_THREADS;
+      k.step_lds = ge_edge_lds_bytes(e->aw_max, e->P.W) + (RAGGED ? GE_EDGE_CLASS_BYTES : 0);  // (+ the class of every slot of the workgroup)
+    }
+  }
+  // parenting >= 2 (multi-class engine: PRUNE 1 when every class fits GE_MAXW words, else PRUNE 2 for all of them -- e->P.W is the
+  // widest class's)
+  if constexpr (ENV == GE_LONGEST_PATH || ENV == GE_TSP) {
+    if (prunes(e->P) && e->P.W > GE_MAXW) { k.step[0] = ge_k_step<ENV, false, RAGGED, 2>; k.step[1] = ge_k_step<ENV, true, RAGGED, 2>; }
+    else if (prunes(e->P)) { k.step[0] = ge_k_step<ENV, false, RAGGED, 1>; k.step[1] = ge_k_step<ENV, true, RAGGED, 1>; }
+  }
+  if constexpr (!RAGGED) {
+    if (path64(e)) {
+      k.step_path64[0][0] = ge_k_step_path64<false, false>; k.step_path64[0][1] = ge_k_step_path64<false, true>;
+      k.step_path64[1][0] = ge_k_step_path64<true, false>; k.step_path64[1][1] = ge_k_step_path64<true, true>;
+    }
+  }
+}
+
+// the dynamic-LDS limit of a kernel the engine selected, for the byte count it is launched with
+static bool raise_lds(const void *kernel, size_t bytes) {
+  (void)kernel;
+  return bytes <= 64 * 1024 || (hipError_t)GE_SET_MAX_DYN_LDS(kernel, bytes) == hipSuccess;
+}
+
+// kernels, launch geometry and LDS limits from e->P (uniform engine) or from the class table (multi-class engine); deletes e on failure
 static int finish_create(ge_engine *e, ge_engine **out) {
   const GeParams &P = e->P;
-  const int nblk = (P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK;
+  const int nblk = step_blocks(P.B);
   const bool rg = e->n_classes > 0;
+  GE_FOR_ENV(P.env_type, if (rg) (select_kernels<ENV, true>(e)); else (select_kernels<ENV, false>(e)));
   // ---- graph kernel
   int reset_lds = P.lds.total, gen_lds = P.ldsf.total, f64_body = 0;
   bool any64 = !rg && P.n <= 64 && !P.spatial;
@@ -257,45 +330,16 @@ static int finish_create(ge_engine *e, ge_engine **out) {
   e->lds_bytes_inject = reset_lds;
   if (!rg && P.nocolw) { GeParams Pi = P; Pi.nocolw = 0; Pi.nowsort = 0; ge_make_lds(Pi, P.B); e->lds_bytes_inject = Pi.lds.total; }
   if (reset_lds > kMaxLds || gen_lds > kMaxLds || e->lds_bytes_inject > kMaxLds) { delete e; return fail(GE_E_TOOBIG, "per-env graph does not fit 160 KiB of LDS"); }
-  int per_cu = kMaxLds / (reset_lds > 0 ? reset_lds : 1);
-  if (per_cu > 16) per_cu = 16;
-  if (per_cu < 1) per_cu = 1;
-  e->reset_grid = 256 * per_cu;
-  if (e->reset_grid > P.B) e->reset_grid = P.B;
+  e->reset_grid = resident_grid(reset_lds, P.B);
   e->nseed = (e->reset_grid + 63) / 64;  // one seeding workgroup per 64 regenerating workgroups: the usual queue fits one round of both
-  hipError_t hr = hipSuccess;
-  if (reset_lds > 64 * 1024 || e->lds_bytes_inject > 64 * 1024) {
-    const int most = reset_lds > e->lds_bytes_inject ? reset_lds : e->lds_bytes_inject;
-    if (rg) GE_FOR_RAGGED_ENV(P.env_type, hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_reset<ENV, true>), reset_lds));
-    else GE_FOR_ENV(P.env_type, hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_reset<ENV, false>), most));
-    if (hr != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the reset kernel"); }
-  }
-  // ---- quad-per-slot step kernel of the edge-action envs: its LDS stage (mask rows + node sets of 256 slots) passes 64 KB
-  if (edge_quad(e) && edge_lds(e) > 64 * 1024) {
-    const int bytes = (int)edge_lds(e);
-    if (P.env_type == GE_STEINER_TREE && rg) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_STEINER_TREE, true, true>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_STEINER_TREE, false, true>), bytes); }
-    else if (rg) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_MULTICAST_ROUTING, true, true>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_MULTICAST_ROUTING, false, true>), bytes); }
-    else if (P.env_type == GE_STEINER_TREE) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_STEINER_TREE, true, false>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_STEINER_TREE, false, false>), bytes); }
-    else { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_MULTICAST_ROUTING, true, false>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step_edge<GE_MULTICAST_ROUTING, false, false>), bytes); }
-    if (hr != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the edge step kernel"); }
-  }
-  // ---- multi-class engine, thread-per-slot step kernel: the LDS stage holds one node set of the widest class per slot
-  if (rg && (size_t)GE_STEP_BLOCK * P.W * 8 + GE_STEP_BLOCK + 64 > 64 * 1024) {
-    const int bytes = (int)((size_t)GE_STEP_BLOCK * P.W * 8 + GE_STEP_BLOCK + 64);
-    const bool pr = (P.env_type == GE_LONGEST_PATH || P.env_type == GE_TSP) && P.parenting >= 2;
-    if (pr && P.env_type == GE_TSP) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_TSP, true, true, 2>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_TSP, false, true, 2>), bytes); }
-    else if (pr) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_LONGEST_PATH, true, true, 2>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_LONGEST_PATH, false, true, 2>), bytes); }
-    else { GE_FOR_RAGGED_ENV(P.env_type, hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<ENV, true, true, 0>), bytes)); if (hr == hipSuccess) GE_FOR_RAGGED_ENV(P.env_type, hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<ENV, false, true, 0>), bytes)); }
-    if (hr != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the step kernel"); }
-  }
-  // ---- thread-per-slot step kernel: its LDS stage (one node set per slot of the workgroup) passes 64 KB above 2 048 nodes
-  if (!rg && (size_t)GE_STEP_BLOCK * P.W * 8 + GE_STEP_BLOCK + 64 > 64 * 1024) {
-    const int bytes = (int)((size_t)GE_STEP_BLOCK * P.W * 8 + GE_STEP_BLOCK + 64);
-    const bool pr = (P.env_type == GE_LONGEST_PATH || P.env_type == GE_TSP) && P.parenting >= 2;
-    if (pr && P.env_type == GE_TSP) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_TSP, true, false, 2>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_TSP, false, false, 2>), bytes); }
-    else if (pr) { hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_LONGEST_PATH, true, false, 2>), bytes); if (hr == hipSuccess) hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<GE_LONGEST_PATH, false, false, 2>), bytes); }
-    else { GE_FOR_ENV(P.env_type, hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<ENV, true, false, 0>), bytes)); if (hr == hipSuccess) GE_FOR_ENV(P.env_type, hr = (hipError_t)GE_SET_MAX_DYN_LDS((ge_k_step<ENV, false, false, 0>), bytes)); }
-    if (hr != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the step kernel"); }
+  // (ge_inject_state on a nocolw engine launches the same kernel on the full carve: the larger of the two sizes)
+  if (!raise_lds((const void *)e->k.reset, reset_lds > e->lds_bytes_inject ? reset_lds : e->lds_bytes_inject)) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the reset kernel"); }
+  // ---- step kernel: the quad-per-slot stage of the edge-action envs (mask rows + node sets of 256 slots) passes 64 KB; the
+  // thread-per-slot stage (one node set per slot of the workgroup) would above 2 048 nodes
+  if (!raise_lds((const void *)e->k.step[0], e->k.step_lds) || !raise_lds((const void *)e->k.step[1], e->k.step_lds)) {
+    const bool quad = e->k.step_quad;
+    delete e;
+    return fail(GE_E_LAUNCH, quad ? "cannot raise the dynamic LDS limit of the edge step kernel" : "cannot raise the dynamic LDS limit of the step kernel");
   }
   // ---- feature kernels
   e->feat_fast = any64 ? 1 : 0;  // (spatial TSP: float64 weights do not fit the fast path's LDS)
@@ -305,16 +349,12 @@ static int finish_create(ge_engine *e, ge_engine **out) {
   e->gen_pre_off = P.ldsf.pre;
   if (rg) { e->gen_pre_off = ge_align16(gen_lds); e->gen_lds = e->gen_pre_off + (nblk + 2) * 4; }
   if (e->feat_lds > kMaxLds || e->gen_lds > kMaxLds) { delete e; return fail(GE_E_TOOBIG, "feature kernel does not fit LDS"); }
-  if (e->gen_lds > 64 * 1024) {
-    hr = rg ? (hipError_t)GE_SET_MAX_DYN_LDS(ge_k_features<true>, e->gen_lds) : (hipError_t)GE_SET_MAX_DYN_LDS(ge_k_features<false>, e->gen_lds);
-    if (hr != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the feature kernel"); }
-  }
-  if (e->feat_fast && e->feat_lds > 64 * 1024) {
-    hr = rg ? (hipError_t)GE_SET_MAX_DYN_LDS(ge_k_features64<true>, e->feat_lds) : (hipError_t)GE_SET_MAX_DYN_LDS(ge_k_features64<false>, e->feat_lds);
-    if (hr != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the n<=64 feature kernel"); }
-  }
-  { int per = kMaxLds / e->gen_lds; if (per > 16) per = 16; if (per < 1) per = 1; e->gen_grid = 256 * per; if (e->gen_grid > P.B) e->gen_grid = P.B; }
-  { int per = kMaxLds / e->feat_lds; if (per > 16) per = 16; if (per < 1) per = 1; e->feat_grid = 256 * per; if (e->feat_grid > P.B) e->feat_grid = P.B; }
+  for (const GeBucket &K : e->bk)  // a bucket of classes with n <= 64 only launches the generic kernel for the fast path's fallback list
+    if (K.used && !K.gen_used && !raise_lds((const void *)e->k.features, K.fb_lds)) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the feature kernel"); }
+  if (!raise_lds((const void *)e->k.features, e->gen_lds)) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the feature kernel"); }
+  if (e->feat_fast && !raise_lds((const void *)e->k.features64, e->feat_lds)) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the n<=64 feature kernel"); }
+  e->gen_grid = resident_grid(e->gen_lds, P.B);
+  e->feat_grid = resident_grid(e->feat_lds, P.B);
   *out = e;
   return GE_OK;
 }
@@ -329,10 +369,7 @@ extern "C" int ge_create(const ge_config *cfg, const ge_buffers *bufs, ge_engine
   P.buf = *bufs;
   ge_engine *e = new (std::nothrow) ge_engine();
   if (!e) return fail(GE_E_BADARG, "out of host memory");
-  e->P = P; e->cfg = *cfg; e->have_events = false;
-  e->loaded = false; e->seeded = false; e->streams = false;
-  e->spares = false; e->period = 0; e->swap_parts = 1; e->pending_calls = 0; memset(&e->RS, 0, sizeof(e->RS));
-  e->n_classes = 0; memset(&e->R, 0, sizeof(e->R)); e->aw_max = P.AW;
+  e->P = P; e->cfg = *cfg; e->aw_max = P.AW;
   return finish_create(e, out);
 }
 
@@ -375,13 +412,12 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
   }
   // parenting >= 2 of LongestPath / TSP: one PRUNE form for the whole engine -- the walks in memory (PRUNE 2) as soon as one class is
   // above GE_MAXW words, and then every class needs its prune_scratch (ge_layout reports none for a class that would fit registers)
-  if ((t == GE_LONGEST_PATH || t == GE_TSP) && cfgs[0].parenting >= 2 && e->classes[widest].W > GE_MAXW)
+  if (prunes(e->classes[widest]) && e->classes[widest].W > GE_MAXW)
     for (int c = 0; c < n_classes; c++)
       if (!bufs[c].prune_scratch) { delete e; return fail(GE_E_BADARG, "parenting >= 2 with a class above 512 nodes runs the residual-graph walks in memory for every class: each class needs prune_scratch ([B_c, 4, W_c] uint64)"); }
   // one launch geometry of the generic feature kernel per LDS bucket: the wave count every class of the bucket can hold -- two
   // workgroups per CU where that leaves at least four waves, else one
-  memset(e->bk, 0, sizeof(e->bk));
-  const int nblk_all = (int)((total + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK);
+  const int nblk_all = step_blocks(total);
   for (int b = 0; b < GE_MAX_BUCKETS; b++) {
     // every class takes the wave count it would choose as a uniform engine; if the bucket's widest allocation then leaves room for
     // ONE workgroup per CU only, the smaller classes are re-derived for the whole CU (up to 16 waves: idle LDS otherwise).  The
@@ -405,14 +441,13 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
     if (!anygen) {  // one wave per slot (ge_make_ldsf: n <= 64), sized for the bucket's largest class
       int fb = 0;
       for (const GeParams &C : e->classes) if (C.bucket == b && C.ldsf.total > fb) fb = C.ldsf.total;
-      K.fb_pre_off = ge_align16(fb); K.fb_lds = K.fb_pre_off + (nblk_all + 2) * 4;
-      if (K.fb_lds > 64 * 1024 && GE_SET_MAX_DYN_LDS(ge_k_features<true>, K.fb_lds) != hipSuccess) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the feature kernel"); }
+      K.fb_pre_off = ge_align16(fb); K.fb_lds = K.fb_pre_off + (nblk_all + 2) * 4;  // (its LDS limit: finish_create, with the other kernels')
     }
     if (K.reset_lds < GE_SEED_LDS_BYTES) K.reset_lds = GE_SEED_LDS_BYTES;
-    { int per = kMaxLds / K.reset_lds; if (per > 16) per = 16; if (per < 1) per = 1; K.reset_grid = 256 * per; if (K.reset_grid > total) K.reset_grid = (int)total; }
+    K.reset_grid = resident_grid(K.reset_lds, total);
     if (anygen) {
       K.gen_pre_off = ge_align16(K.gen_lds); K.gen_lds = K.gen_pre_off + (nblk_all + 2) * 4;
-      int per = kMaxLds / K.gen_lds; if (per > 16) per = 16; if (per < 1) per = 1; K.gen_grid = 256 * per; if (K.gen_grid > total) K.gen_grid = (int)total;
+      K.gen_grid = resident_grid(K.gen_lds, total);
     }
   }
   // engine-wide block: the widest class's geometry (LDS stage of the step kernel), all slots, the global arrays of class 0
@@ -422,8 +457,6 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
   e->P.buf = bufs[0];
   e->P.env_index_base = cfgs[0].env_index_base;
   e->cfg = cfgs[0]; e->cfg.num_envs = (int32_t)total;
-  e->have_events = false; e->loaded = false; e->seeded = false; e->streams = false;
-  e->spares = false; e->period = 0; e->swap_parts = 1; e->pending_calls = 0; memset(&e->RS, 0, sizeof(e->RS));
   e->n_classes = n_classes;
   e->aw_max = aw_max;
   e->P.AW = aw_max;  // (the edge step kernel's LDS stage: the widest mask row, which for the edge-action envs need not be the widest class's)
@@ -531,12 +564,10 @@ static int launch_seed(ge_engine *e, const uint32_t *seeds, int jlo, void *strea
 
 // V: the engine (e->P) or its spare-image view (e->PS); VR: the matching class table
 static int launch_combine(ge_engine *e, const GeParams &V, const GeRagged &VR, GeRun run, bool small, void *stream) {
-  const bool rg = e->n_classes > 0;
-  size_t lds = (size_t)((V.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK + 2) * 4;
+  size_t lds = (size_t)(step_blocks(V.B) + 2) * 4;
   int64_t items = (int64_t)(run.items == GE_ITEMS_ALL ? V.B : (small ? 64 : 4096)) * V.n;
   int grid = (int)((items + 255) / 256); if (grid > 8192) grid = 8192;
-  if (rg) GE_LAUNCH(ge_k_feat_combine<true>, grid, 256, lds, stream, V, VR, run);
-  else GE_LAUNCH(ge_k_feat_combine<false>, grid, 256, lds, stream, V, VR, run);
+  GE_LAUNCH(e->k.feat_combine, grid, 256, lds, stream, V, VR, run);
   return check_launch("feature combine kernel");
 }
 
@@ -548,8 +579,7 @@ static int launch_features(ge_engine *e, const GeParams &V, const GeRagged &VR, 
   if (small && fgrid > 64) fgrid = 64;
   const int gen_threads = GE_WAVE * (rg ? e->classes[0].ldsf.waves : V.ldsf.waves);
   if (e->feat_fast) {
-    if (rg) GE_LAUNCH(ge_k_features64<true>, fgrid, GE_F64_THREADS, e->feat_lds, stream, V, VR, run, e->feat64_pre_off);
-    else GE_LAUNCH(ge_k_features64<false>, fgrid, GE_F64_THREADS, e->feat_lds, stream, V, VR, run, e->feat64_pre_off);
+    GE_LAUNCH(e->k.features64, fgrid, GE_F64_THREADS, e->feat_lds, stream, V, VR, run, e->feat64_pre_off);
     rc = check_launch("feature kernel (n <= 64)");
     if (rc != GE_OK) return rc;
     // the fast path's fallback list (normally empty); multi-class engine: every slot of a class with n > 64, feat_parts workgroups each
@@ -558,20 +588,20 @@ static int launch_features(ge_engine *e, const GeParams &V, const GeRagged &VR, 
         const GeBucket &K = e->bk[b];
         if (!K.used) continue;
         if (!K.gen_used) {  // classes with n <= 64 only: the list holds the rare slots too deep for the fast path (eight workgroups, as in a uniform engine)
-          GE_LAUNCH(ge_k_features<true>, 8, GE_WAVE, K.fb_lds, stream, V, VR, as_list(run), K.fb_pre_off, b);
+          GE_LAUNCH(e->k.features, 8, GE_WAVE, K.fb_lds, stream, V, VR, as_list(run), K.fb_pre_off, b);
           rc = check_launch("feature kernel (fallback list)");
           continue;
         }
         int64_t want = (int64_t)K.gen_grid * ge_feat_workgroups(V.feat_parts) * (queue ? 1 : 4);
         if (small && want > 288) want = 288;
         if (want > 65535 * 16) want = 65535 * 16;
-        GE_LAUNCH(ge_k_features<true>, (int)want, GE_WAVE * K.gen_waves, K.gen_lds, stream, V, VR, as_list(run), K.gen_pre_off, b);
+        GE_LAUNCH(e->k.features, (int)want, GE_WAVE * K.gen_waves, K.gen_lds, stream, V, VR, as_list(run), K.gen_pre_off, b);
         rc = check_launch("feature kernel (list)");
       }
       return (rc == GE_OK && V.feat_parts > 1) ? launch_combine(e, V, VR, as_list(run), small, stream) : rc;
     }
     int g2 = e->gen_grid < 8 ? e->gen_grid : 8;  // (the list is normally empty and a handful of slots at most: eight workgroups dispatch in less time than 64 -- the launch is on every step's critical path)
-    GE_LAUNCH(ge_k_features<false>, g2, gen_threads, e->gen_lds, stream, V, VR, as_list(run), e->gen_pre_off, -1);
+    GE_LAUNCH(e->k.features, g2, gen_threads, e->gen_lds, stream, V, VR, as_list(run), e->gen_pre_off, -1);
     return check_launch("feature kernel (fallback list)");
   }
   {
@@ -583,11 +613,11 @@ static int launch_features(ge_engine *e, const GeParams &V, const GeRagged &VR, 
       for (int b = 0; b < GE_MAX_BUCKETS && rc == GE_OK; b++) {
         const GeBucket &K = e->bk[b];
         if (!K.gen_used) continue;
-        GE_LAUNCH(ge_k_features<true>, (int)want, GE_WAVE * K.gen_waves, K.gen_lds, stream, V, VR, run, K.gen_pre_off, b);
+        GE_LAUNCH(e->k.features, (int)want, GE_WAVE * K.gen_waves, K.gen_lds, stream, V, VR, run, K.gen_pre_off, b);
         rc = check_launch("feature kernel");
       }
     }
-    else GE_LAUNCH(ge_k_features<false>, (int)want, gen_threads, e->gen_lds, stream, V, VR, run, e->gen_pre_off, -1);
+    else GE_LAUNCH(e->k.features, (int)want, gen_threads, e->gen_lds, stream, V, VR, run, e->gen_pre_off, -1);
   }
   rc = check_launch("feature kernel");
   if (rc != GE_OK || V.feat_parts == 1) return rc;
@@ -598,30 +628,22 @@ static int launch_features(ge_engine *e, const GeParams &V, const GeRagged &VR, 
 // Kou) for the regenerated slots, on the slabs the graph kernel wrote.  Multi-class engine: one launch over all slots; every item
 // finds its class and runs on that class's eval_scratch (VR: the live or the spare class table)
 static int launch_seq_baseline(ge_engine *e, const GeParams &P, const GeRagged &VR, int queue, void *stream) {
-  const bool rg = e->n_classes > 0;
-  const uint64_t slot_bytes = rg ? 0 : eval_slot_bytes(P);
-  const int nblk = (P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK;
+  const uint64_t slot_bytes = e->n_classes > 0 ? 0 : eval_slot_bytes(P);
+  const int nblk = step_blocks(P.B);
+  int g = (P.B + GE_TSP_EVAL_THREADS - 1) / GE_TSP_EVAL_THREADS; if (g > 4096) g = 4096;  // one thread per item
   if (P.env_type == GE_MAX_INDEPENDENT_SET) {
-    int g = (P.B + GE_TSP_EVAL_THREADS - 1) / GE_TSP_EVAL_THREADS; if (g > 4096) g = 4096;
-    if (rg) GE_LAUNCH(ge_k_mis_baseline<true>, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
-    else GE_LAUNCH(ge_k_mis_baseline<false>, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+    GE_LAUNCH(e->k.mis_baseline, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
     return check_launch("MaxIndependentSet baseline kernel");
   }
   if (P.env_type == GE_STEINER_TREE) {
-    int g = (P.B + GE_TSP_EVAL_THREADS - 1) / GE_TSP_EVAL_THREADS; if (g > 4096) g = 4096;
-    if (rg) GE_LAUNCH(ge_k_steiner_baseline<true>, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
-    else GE_LAUNCH(ge_k_steiner_baseline<false>, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+    GE_LAUNCH(e->k.steiner_baseline, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
     return check_launch("SteinerTree baseline kernel");
   }
   const int pre_off = GE_WAVE * P.W * 8;  // (P.W: the widest class's in a multi-class engine)
-  int grid = P.B < 2048 ? P.B : 2048;
-  if (rg) GE_LAUNCH(ge_k_tsp_closure<true>, grid, GE_TSP_EVAL_THREADS, pre_off + (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes, pre_off);
-  else GE_LAUNCH(ge_k_tsp_closure<false>, grid, GE_TSP_EVAL_THREADS, pre_off + (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes, pre_off);
+  GE_LAUNCH(e->k.tsp_closure, P.B < 2048 ? P.B : 2048, GE_TSP_EVAL_THREADS, pre_off + (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes, pre_off);
   int rc = check_launch("TSP baseline: closure kernel");
   if (rc != GE_OK) return rc;
-  grid = (P.B + GE_TSP_EVAL_THREADS - 1) / GE_TSP_EVAL_THREADS; if (grid > 4096) grid = 4096;
-  if (rg) GE_LAUNCH(ge_k_tsp_tour<true>, grid, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
-  else GE_LAUNCH(ge_k_tsp_tour<false>, grid, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+  GE_LAUNCH(e->k.tsp_tour, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
   return check_launch("TSP baseline: tour kernel");
 }
 
@@ -654,15 +676,15 @@ static int launch_reset(ge_engine *e, const GeParams &V, const GeRagged &VR, con
       const int g = queue ? bg + ns : (V.B < K.reset_grid * 4 ? V.B : K.reset_grid * 4);
       int lds = K.reset_lds;
       GeParams V2 = V;
-      if (V.lds.pre != 0) { V2.lds.pre = ge_align16(K.reset_lds); lds = V2.lds.pre + ((V.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK + 2) * 4; }  // queue prefix behind the bucket's scratch
-      GE_FOR_RAGGED_ENV(V.env_type, GE_LAUNCH((ge_k_reset<ENV, true>), g, GE_RESET_THREADS, lds, stream, V2, VR, seeds, run, inj, ns, b));
+      if (V.lds.pre != 0) { V2.lds.pre = ge_align16(K.reset_lds); lds = V2.lds.pre + (step_blocks(V.B) + 2) * 4; }  // queue prefix behind the bucket's scratch
+      GE_LAUNCH(e->k.reset, g, GE_RESET_THREADS, lds, stream, V2, VR, seeds, run, inj, ns, b);
       rc = check_launch("reset kernel");
       first = false;
     }
   } else if (run.inject && V.nocolw) {  // the injected rows come in the caller's order: this launch keeps the {neighbour, code} list (the full LDS carve)
     GeParams Vi = V; Vi.nocolw = 0; Vi.nowsort = 0; ge_make_lds(Vi, V.B);
-    GE_FOR_ENV(V.env_type, GE_LAUNCH((ge_k_reset<ENV, false>), grid, GE_RESET_THREADS, e->lds_bytes_inject, stream, Vi, VR, seeds, run, inj, nseed, -1));
-  } else GE_FOR_ENV(V.env_type, GE_LAUNCH((ge_k_reset<ENV, false>), grid, GE_RESET_THREADS, e->lds_bytes, stream, V, VR, seeds, run, inj, nseed, -1));
+    GE_LAUNCH(e->k.reset, grid, GE_RESET_THREADS, e->lds_bytes_inject, stream, Vi, VR, seeds, run, inj, nseed, -1);
+  } else GE_LAUNCH(e->k.reset, grid, GE_RESET_THREADS, e->lds_bytes, stream, V, VR, seeds, run, inj, nseed, -1);
   if (rc == GE_OK) rc = check_launch("reset kernel");
   if (rc != GE_OK) return rc;
   bool baseline = eval_slot_bytes(V) != 0;
@@ -677,13 +699,11 @@ static int launch_reset(ge_engine *e, const GeParams &V, const GeRagged &VR, con
 
 // every image is empty; with seeded generator states refill them all right away (one pass at full occupancy)
 static int refill_spares(ge_engine *e, void *stream) {
-  const int nblk = (e->P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK;
-  GE_LAUNCH(ge_k_refill_list, nblk, GE_STEP_BLOCK, 64, stream, e->P, e->refill_list, e->refill_count);
+  GE_LAUNCH(ge_k_refill_list, step_blocks(e->P.B), GE_STEP_BLOCK, 64, stream, e->P, e->refill_list, e->refill_count);
   int rc = check_launch("refill list kernel");
   if (rc != GE_OK) return rc;
-  GeInject none = {nullptr, nullptr, nullptr, nullptr, nullptr};
   e->pending_calls = 0;
-  return launch_reset(e, e->PS, e->RS, nullptr, run_refill(), none, false, stream);
+  return launch_reset(e, e->PS, e->RS, nullptr, run_refill(), kNoInject, false, stream);
 }
 static int invalidate_spares(ge_engine *e, void *stream) {
   if (!e->spares) return GE_OK;
@@ -694,7 +714,7 @@ static int invalidate_spares(ge_engine *e, void *stream) {
 // a full reset / injection leaves the finished-slot queues empty: the regeneration queue and, with spares, the swap queue (next-step
 // autoreset consumes it at the START of the next ge_step: a stale entry would copy an image over the slot that was just reset)
 static int clear_queue(ge_engine *e, void *stream) {
-  const size_t bytes = sizeof(int32_t) * (size_t)((e->P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK);
+  const size_t bytes = sizeof(int32_t) * (size_t)step_blocks(e->P.B);
   if (hipMemsetAsync(e->P.buf.reset_count, 0, bytes, (hipStream_t)stream) != hipSuccess) return fail(GE_E_LAUNCH, "hipMemsetAsync failed");
   if (e->spares && hipMemsetAsync(e->P.swap_count, 0, bytes, (hipStream_t)stream) != hipSuccess) return fail(GE_E_LAUNCH, "hipMemsetAsync failed");
   return GE_OK;
@@ -702,10 +722,9 @@ static int clear_queue(ge_engine *e, void *stream) {
 
 extern "C" int ge_reset(ge_engine *e, const uint32_t *seeds, void *stream) {
   if (!e || !seeds) return fail(GE_E_BADARG, "null argument");
-  GeInject none = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int rc = clear_queue(e, stream);
   if (rc != GE_OK) return rc;
-  rc = launch_reset(e, e->P, e->R, seeds, run_full(), none, false, stream);
+  rc = launch_reset(e, e->P, e->R, seeds, run_full(), kNoInject, false, stream);
   if (rc == GE_OK) e->loaded = true;
   if (rc == GE_OK) rc = invalidate_spares(e, stream);  // ... and refill: every slot's episode 1 waits in its image
   return rc;
@@ -717,10 +736,9 @@ extern "C" int ge_reset_continue(ge_engine *e, void *stream) {
   if (e->spares) return fail(GE_E_UNSUPPORTED, "ge_reset_continue on an engine with spares: an image generated ahead of time would leave the streams of the wrong episode behind");
   if (!e->P.buf.stream_state) return fail(GE_E_STATE, "ge_reset_continue needs ge_buffers.stream_state (the streams every reset leaves behind)");
   if (!e->loaded || !e->seeded || !e->streams) return fail(GE_E_STATE, "ge_reset_continue before ge_reset: there is no stream to continue");
-  GeInject none = {nullptr, nullptr, nullptr, nullptr, nullptr};
   int rc = clear_queue(e, stream);
   if (rc != GE_OK) return rc;
-  return launch_reset(e, e->P, e->R, nullptr, run_continue(), none, false, stream);
+  return launch_reset(e, e->P, e->R, nullptr, run_continue(), kNoInject, false, stream);
 }
 
 extern "C" int ge_inject_state(ge_engine *e, const int64_t *links, const uint8_t *wcode, const float *x,
@@ -742,50 +760,14 @@ extern "C" int ge_inject_state(ge_engine *e, const int64_t *links, const uint8_t
   return rc;
 }
 
-static size_t step_lds(const ge_engine *e) { return (size_t)GE_STEP_BLOCK * e->P.W * 8 + GE_STEP_BLOCK + 64; }
-
 extern "C" int ge_sample_actions(ge_engine *e, uint64_t policy_seed, int64_t *actions, void *stream);
 
-// parenting >= 2 of LongestPath / TSP: the instantiation of the step kernel that carries the residual-graph walks (multi-class
-// engine: PRUNE 1 when every class fits GE_MAXW words, else PRUNE 2 for all of them -- e->P.W is the widest class's)
-static bool prunes(const ge_engine *e) { return (e->P.env_type == GE_LONGEST_PATH || e->P.env_type == GE_TSP) && e->P.parenting >= 2; }
-#define GE_LAUNCH_STEP_RAGGED(SAMPLE, actions_arg, seed_arg)                                                                            \
-  do {                                                                                                                                  \
-    if (edge_quad(e) && e->P.env_type == GE_STEINER_TREE) GE_LAUNCH((ge_k_step_edge<GE_STEINER_TREE, SAMPLE, true>), grid, GE_EDGE_THREADS, edge_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else if (edge_quad(e)) GE_LAUNCH((ge_k_step_edge<GE_MULTICAST_ROUTING, SAMPLE, true>), grid, GE_EDGE_THREADS, edge_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else if (prunes(e) && e->P.env_type == GE_TSP && e->P.W > GE_MAXW) GE_LAUNCH((ge_k_step<GE_TSP, SAMPLE, true, 2>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else if (prunes(e) && e->P.W > GE_MAXW) GE_LAUNCH((ge_k_step<GE_LONGEST_PATH, SAMPLE, true, 2>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else if (prunes(e) && e->P.env_type == GE_TSP) GE_LAUNCH((ge_k_step<GE_TSP, SAMPLE, true, 1>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else if (prunes(e)) GE_LAUNCH((ge_k_step<GE_LONGEST_PATH, SAMPLE, true, 1>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else GE_FOR_RAGGED_ENV(e->P.env_type, GE_LAUNCH((ge_k_step<ENV, SAMPLE, true, 0>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg)); \
-  } while (0)
-#define GE_LAUNCH_STEP(SAMPLE, actions_arg, seed_arg)                                                                                   \
-  do {                                                                                                                                  \
-    if (e->n_classes > 0) GE_LAUNCH_STEP_RAGGED(SAMPLE, actions_arg, seed_arg);                                                         \
-    else if (path64(e) && e->spares) GE_LAUNCH((ge_k_step_path64<SAMPLE, true>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, actions_arg, seed_arg);  \
-    else if (path64(e)) GE_LAUNCH((ge_k_step_path64<SAMPLE, false>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, actions_arg, seed_arg);  \
-    else if (edge_quad(e) && e->P.env_type == GE_STEINER_TREE) GE_LAUNCH((ge_k_step_edge<GE_STEINER_TREE, SAMPLE, false>), grid, GE_EDGE_THREADS, edge_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else if (edge_quad(e)) GE_LAUNCH((ge_k_step_edge<GE_MULTICAST_ROUTING, SAMPLE, false>), grid, GE_EDGE_THREADS, edge_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else if (prunes(e) && e->P.env_type == GE_TSP && e->P.W > GE_MAXW) GE_LAUNCH((ge_k_step<GE_TSP, SAMPLE, false, 2>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else if (prunes(e) && e->P.W > GE_MAXW) GE_LAUNCH((ge_k_step<GE_LONGEST_PATH, SAMPLE, false, 2>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else if (prunes(e) && e->P.env_type == GE_TSP) GE_LAUNCH((ge_k_step<GE_TSP, SAMPLE, false, 1>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else if (prunes(e)) GE_LAUNCH((ge_k_step<GE_LONGEST_PATH, SAMPLE, false, 1>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg); \
-    else GE_FOR_ENV(e->P.env_type, GE_LAUNCH((ge_k_step<ENV, SAMPLE, false, 0>), grid, GE_STEP_BLOCK, step_lds(e), stream, e->P, e->R, actions_arg, seed_arg)); \
-  } while (0)
-
-static bool path64(const ge_engine *e);
-static size_t step_lds(const ge_engine *e);
-// SteinerTree / MulticastRouting whose mask rows fit the LDS stage of the quad-per-slot kernel (ge_step.h, ge_k_step_edge); a
-// multi-class engine stages every row with the stride of its widest class (e->aw_max) and node sets of its widest class (e->P.W)
-static bool edge_quad(const ge_engine *e) {
-  static const bool off = getenv("GE_NO_EDGE_QUAD") != nullptr;  // diagnostic: the thread-per-slot kernel (before / after measurements)
-  return !off && (e->P.env_type == GE_STEINER_TREE || e->P.env_type == GE_MULTICAST_ROUTING) && ge_edge_fits(e->aw_max, e->P.W);
-}
-// (+ the class of every slot of the workgroup in a multi-class engine)
-static size_t edge_lds(const ge_engine *e) { return ge_edge_lds_bytes(e->aw_max, e->P.W) + (e->n_classes > 0 ? GE_EDGE_CLASS_BYTES : 0); }
-
-static bool path64(const ge_engine *e) {
-  return e->n_classes == 0 && (e->P.env_type == GE_SHORTEST_PATH || e->P.env_type == GE_LONGEST_PATH) && e->P.W == 1 && e->P.parenting < 2;
+// the step kernel the engine selected; sample: the fused device policy draws the actions from policy_seed, else they are `actions`
+static void launch_step(ge_engine *e, bool sample, const int64_t *actions, uint64_t policy_seed, void *stream) {
+  const GeKernels &k = e->k;
+  const int grid = step_blocks(e->P.B);
+  if (path64(e)) GE_LAUNCH(k.step_path64[sample][e->spares], grid, k.step_threads, k.step_lds, stream, e->P, actions, policy_seed);
+  else GE_LAUNCH(k.step[sample], grid, k.step_threads, k.step_lds, stream, e->P, e->R, actions, policy_seed);
 }
 
 // DistributionCenter with n <= 64 (in a multi-class engine: in any class) computes a centre's coverage range when it is chosen
@@ -809,13 +791,12 @@ extern "C" int ge_step_only(ge_engine *e, const int64_t *actions, void *stream) 
   int rc = check_state(e);
   if (rc != GE_OK) return rc;
   if (dc_range(e)) {  // the chosen centres' coverage ranges, computed when they are chosen
-    if (e->n_classes > 0) GE_LAUNCH(ge_k_dc_range<true>, (e->P.B + GE_WAVE - 1) / GE_WAVE, GE_WAVE, (size_t)64 * GE_WAVE * 8 + GE_WAVE * 64, stream, e->P, e->R, actions);
-    else GE_LAUNCH(ge_k_dc_range<false>, (e->P.B + GE_WAVE - 1) / GE_WAVE, GE_WAVE, (size_t)e->P.n * GE_WAVE * 8 + GE_WAVE * 64, stream, e->P, e->R, actions);
+    const int rows = e->n_classes > 0 ? 64 : e->P.n;  // distance columns per lane (multi-class engine: of the largest class that takes this path)
+    GE_LAUNCH(e->k.dc_range, (e->P.B + GE_WAVE - 1) / GE_WAVE, GE_WAVE, (size_t)rows * GE_WAVE * 8 + GE_WAVE * 64, stream, e->P, e->R, actions);
     rc = check_launch("coverage range kernel");
     if (rc != GE_OK) return rc;
   }
-  int grid = (e->P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK;
-  GE_LAUNCH_STEP(false, actions, (uint64_t)0);
+  launch_step(e, false, actions, 0, stream);
   return check_launch("step kernel");
 }
 
@@ -829,8 +810,7 @@ static int sample_and_step(ge_engine *e, uint64_t policy_seed, int64_t *scratch,
     rc = ge_sample_actions(e, policy_seed, scratch, stream);
     return rc == GE_OK ? ge_step_only(e, scratch, stream) : rc;
   }
-  int grid = (e->P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK;
-  GE_LAUNCH_STEP(true, (const int64_t *)nullptr, policy_seed);
+  launch_step(e, true, nullptr, policy_seed, stream);
   return check_launch("fused sample+step kernel");
 }
 
@@ -840,17 +820,14 @@ extern "C" int ge_reset_pending(ge_engine *e, void *stream) {
   int rc = check_state(e);
   if (rc != GE_OK) return rc;
   if (e->P.autoreset) {
-    GeInject none = {nullptr, nullptr, nullptr, nullptr, nullptr};
     if (e->spares) {  // finished slots with a valid image: one streaming copy each
-      const int nblk = (e->P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK;
       int64_t grid = 1024;  // workgroups stride over (slot, part) items; most steps have a few hundred
       if (grid > (int64_t)e->P.B * e->swap_parts) grid = (int64_t)e->P.B * e->swap_parts;
-      if (e->n_classes > 0) GE_LAUNCH(ge_k_swap<true>, (int)grid, 256, (nblk + 2) * 4, stream, e->P, e->R, e->RS, e->PS.buf, e->swap_parts);
-      else GE_LAUNCH(ge_k_swap<false>, (int)grid, 256, (nblk + 2) * 4, stream, e->P, e->R, e->RS, e->PS.buf, e->swap_parts);
+      GE_LAUNCH(e->k.swap, (int)grid, 256, (step_blocks(e->P.B) + 2) * 4, stream, e->P, e->R, e->RS, e->PS.buf, e->swap_parts);
       rc = check_launch("swap kernel");
       if (rc != GE_OK) return rc;
     }
-    rc = launch_reset(e, e->P, e->R, nullptr, run_queue(e), none, e->spares, stream);  // (with spares: the slots that finished again before their image was refilled)
+    rc = launch_reset(e, e->P, e->R, nullptr, run_queue(e), kNoInject, e->spares, stream);  // (with spares: the slots that finished again before their image was refilled)
     if (rc == GE_OK && e->spares && ++e->pending_calls >= e->period) rc = refill_spares(e, stream);
   }
   return rc;
@@ -878,30 +855,23 @@ extern "C" int ge_mark_restored(ge_engine *e) {
 
 extern "C" int ge_vectorize(ge_engine *e, float *out, void *stream) {
   if (!e || !out) return fail(GE_E_BADARG, "null argument");
-  if (e->n_classes > 0) {  // multi-class engine: the classes' flat vectors follow one another, class after class
-    for (const GeParams &C : e->classes) {
-      const int64_t Lc = (int64_t)C.n * C.F + (int64_t)C.E * C.Fe + 2 * (int64_t)C.E, tot = (int64_t)C.B * Lc;
-      int64_t blocks = (tot + 255) / 256; if (blocks > 256 * 32) blocks = 256 * 32;
-      GE_LAUNCH(ge_k_vectorize, (int)blocks, 256, 0, stream, C, out);
-      int rc = check_launch("vectorize kernel");
-      if (rc != GE_OK) return rc;
-      out += tot;
-    }
-    return GE_OK;
+  // multi-class engine: the classes' flat vectors follow one another, class after class
+  const GeParams *first = e->n_classes > 0 ? e->classes.data() : &e->P;
+  for (const GeParams *C = first; C < first + (e->n_classes > 0 ? e->n_classes : 1); C++) {
+    const int64_t tot = (int64_t)C->B * obs_len(*C);
+    int64_t blocks = (tot + 255) / 256; if (blocks > 256 * 32) blocks = 256 * 32;
+    GE_LAUNCH(ge_k_vectorize, (int)blocks, 256, 0, stream, *C, out);
+    int rc = check_launch("vectorize kernel");
+    if (rc != GE_OK) return rc;
+    out += tot;
   }
-  int64_t L = (int64_t)e->P.n * e->P.F + (int64_t)e->P.E * e->P.Fe + 2 * (int64_t)e->P.E;
-  int64_t total = (int64_t)e->P.B * L;
-  int64_t blocks = (total + 255) / 256;
-  if (blocks > 256 * 32) blocks = 256 * 32;
-  GE_LAUNCH(ge_k_vectorize, (int)blocks, 256, 0, stream, e->P, out);
-  return check_launch("vectorize kernel");
+  return GE_OK;
 }
 
 extern "C" int ge_sample_actions(ge_engine *e, uint64_t policy_seed, int64_t *actions, void *stream) {
   if (!e || !actions) return fail(GE_E_BADARG, "null argument");
   int grid = (e->P.B + 255) / 256;
-  if (e->n_classes > 0) GE_LAUNCH(ge_k_sample<true>, grid, 256, 0, stream, e->P, e->R, policy_seed, actions);
-  else GE_LAUNCH(ge_k_sample<false>, grid, 256, 0, stream, e->P, e->R, policy_seed, actions);
+  GE_LAUNCH(e->k.sample, grid, 256, 0, stream, e->P, e->R, policy_seed, actions);
   return check_launch("sample kernel");
 }
 
@@ -917,10 +887,16 @@ extern "C" int ge_random_rollout(ge_engine *e, uint64_t policy_seed, int32_t n_s
   return GE_OK;
 }
 
+// the timing events of the ge_timed_* calls, created at the first of them
+static int ensure_events(ge_engine *e) {
+  if (!e->have_events) { for (int k = 0; k < 4; k++) if (hipEventCreate(&e->ev[k]) != hipSuccess) return fail(GE_E_LAUNCH, "hipEventCreate failed"); e->have_events = true; }
+  return GE_OK;
+}
+
 extern "C" int ge_timed_rollout(ge_engine *e, uint64_t policy_seed, int32_t n_steps, int64_t *scratch, void *stream,
                                 double *step_ms, double *reset_ms, double *policy_ms) {
   if (!e || (!scratch && !path64(e))) return fail(GE_E_BADARG, "null argument");
-  if (!e->have_events) { for (int k = 0; k < 4; k++) if (hipEventCreate(&e->ev[k]) != hipSuccess) return fail(GE_E_LAUNCH, "hipEventCreate failed"); e->have_events = true; }
+  if (ensure_events(e) != GE_OK) return GE_E_LAUNCH;
   double ts = 0, tr = 0, tp = 0;
   hipStream_t st = (hipStream_t)stream;
   for (int s = 0; s < n_steps; s++) {
@@ -947,7 +923,7 @@ extern "C" int ge_timed_rollout(ge_engine *e, uint64_t policy_seed, int32_t n_st
 
 extern "C" int ge_timed_step_burst(ge_engine *e, uint64_t policy_seed, int32_t k, int64_t *scratch, void *stream, double *burst_ms) {
   if (!e || !burst_ms) return fail(GE_E_BADARG, "null argument");
-  if (!e->have_events) { for (int j = 0; j < 4; j++) if (hipEventCreate(&e->ev[j]) != hipSuccess) return fail(GE_E_LAUNCH, "hipEventCreate failed"); e->have_events = true; }
+  if (ensure_events(e) != GE_OK) return GE_E_LAUNCH;
   hipStream_t st = (hipStream_t)stream;
   (void)hipEventRecord(e->ev[0], st);
   for (int j = 0; j < k; j++) { int rc = sample_and_step(e, policy_seed, scratch, stream); if (rc != GE_OK) return rc; }
@@ -963,12 +939,10 @@ extern "C" int ge_timed_step_burst(ge_engine *e, uint64_t policy_seed, int32_t k
 GE_KERNEL ge_k_empty(int) {}
 extern "C" int ge_timed_empty_burst(ge_engine *e, int32_t k, void *stream, double *burst_ms) {
   if (!e || !burst_ms) return fail(GE_E_BADARG, "null argument");
-  if (!e->have_events) { for (int j = 0; j < 4; j++) if (hipEventCreate(&e->ev[j]) != hipSuccess) return fail(GE_E_LAUNCH, "hipEventCreate failed"); e->have_events = true; }
+  if (ensure_events(e) != GE_OK) return GE_E_LAUNCH;
   hipStream_t st = (hipStream_t)stream;
-  const int grid = (e->P.B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK;
-  const bool quad = edge_quad(e);
   (void)hipEventRecord(e->ev[0], st);
-  for (int j = 0; j < k; j++) GE_LAUNCH(ge_k_empty, grid, quad ? GE_EDGE_THREADS : GE_STEP_BLOCK, quad ? edge_lds(e) : step_lds(e), stream, 0);
+  for (int j = 0; j < k; j++) GE_LAUNCH(ge_k_empty, step_blocks(e->P.B), e->k.step_threads, e->k.step_lds, stream, 0);
   (void)hipEventRecord(e->ev[1], st);
   if (hipEventSynchronize(e->ev[1]) != hipSuccess) return fail(GE_E_LAUNCH, "hipEventSynchronize failed");
   float ms = 0.f;
@@ -985,7 +959,7 @@ extern "C" int ge_debug_occupancy(ge_engine *e, int *out4) {
   GE_FOR_ENV(e->P.env_type, (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, (ge_k_reset<ENV, false>), GE_RESET_THREADS, e->lds_bytes));
   (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, ge_k_features64<false>, GE_F64_THREADS, e->feat_lds);
   (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, ge_k_features<false>, GE_WAVE * e->P.ldsf.waves, e->P.ldsf.total);
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&d, (ge_k_step_path64<true, false>), GE_STEP_BLOCK, step_lds(e));
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&d, (ge_k_step_path64<true, false>), GE_STEP_BLOCK, e->k.step_lds);
   out4[0] = a; out4[1] = b; out4[2] = c; out4[3] = d;
   return GE_OK;
 }
