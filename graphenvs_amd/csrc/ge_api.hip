@@ -138,6 +138,14 @@ static bool prunes(const GeParams &P) { return (P.env_type == GE_LONGEST_PATH ||
     }                                                                                        \
   } while (0)
 
+// GeParams.nocolw engines: ge_inject_state runs the graph kernel on the full LDS carve (the injected rows need the {neighbour, code}
+// list the reset of such an engine does without)
+static int inject_lds_bytes(const GeParams &P, int queue_B) {
+  if (!P.nocolw) return P.lds.total;
+  GeParams Pi = P; Pi.nocolw = 0; Pi.nowsort = 0; ge_make_lds(Pi, queue_B);
+  return Pi.lds.total;
+}
+
 static int derive(const ge_config *cfg, GeParams &P, int queue_B = 0) {
   if (!cfg) return fail(GE_E_BADARG, "null config");
   memset(&P, 0, sizeof(P));
@@ -206,10 +214,15 @@ static int derive(const ge_config *cfg, GeParams &P, int queue_B = 0) {
   if (cfg->num_envs > 8192 * GE_STEP_BLOCK) return fail(GE_E_TOOBIG, "num_envs > 2M per engine");
   P.nocolw = (t == GE_TSP && P.complete && ng == n && !P.is_eval && !P.spatial && !getenv("GE_KEEP_COLW")) ? 1 : 0;
   P.nowsort = (P.nocolw && n > 64) ? 1 : 0;
-  ge_make_lds(P, queue_B > 0 ? queue_B : P.B);
-  ge_make_ldsf(P, queue_B > 0 ? queue_B : P.B);
+  const int qB = queue_B > 0 ? queue_B : P.B;
+  ge_make_lds(P, qB);
+  ge_make_ldsf(P, qB);
   ge_tune_feat_parts(P);
-  if (P.lds.total > kMaxLds || P.ldsf.total > kMaxLds) return fail(GE_E_TOOBIG, "per-env graph does not fit 160 KiB of LDS");
+  // every carve finish_create launches with, so that the layout query refuses what ge_create / ge_create_ragged would: the graph
+  // kernel's (ge_inject_state included), and the two a multi-class engine lengthens by a second queue prefix behind its widest class
+  const int pre2 = (step_blocks(qB) + 2) * 4;
+  const int reset_need = P.lds.total + (P.lds.pre != 0 ? pre2 : 0), inject_need = inject_lds_bytes(P, qB);
+  if (reset_need > kMaxLds || inject_need > kMaxLds || P.ldsf.total + pre2 > kMaxLds) return fail(GE_E_TOOBIG, "per-env graph does not fit 160 KiB of LDS");
   return GE_OK;
 }
 
@@ -328,7 +341,7 @@ static int finish_create(ge_engine *e, ge_engine **out) {
   if (rg && e->P.lds.pre != 0) { e->P.lds.pre = ge_align16(reset_lds); reset_lds = e->P.lds.pre + (nblk + 2) * 4; }  // prefix behind every class's scratch
   e->lds_bytes = reset_lds;
   e->lds_bytes_inject = reset_lds;
-  if (!rg && P.nocolw) { GeParams Pi = P; Pi.nocolw = 0; Pi.nowsort = 0; ge_make_lds(Pi, P.B); e->lds_bytes_inject = Pi.lds.total; }
+  if (!rg) e->lds_bytes_inject = inject_lds_bytes(P, P.B);
   if (reset_lds > kMaxLds || gen_lds > kMaxLds || e->lds_bytes_inject > kMaxLds) { delete e; return fail(GE_E_TOOBIG, "per-env graph does not fit 160 KiB of LDS"); }
   e->reset_grid = resident_grid(reset_lds, P.B);
   e->nseed = (e->reset_grid + 63) / 64;  // one seeding workgroup per 64 regenerating workgroups: the usual queue fits one round of both

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .vector_env import GraphBatch, VectorGraphEnv, normalize_kwargs
+from .vector_env import GraphBatch, VectorGraphEnv, engine_library, make_config, normalize_kwargs
 
 # per-slot arrays kept engine-wide (class c owns rows [start_c, start_c + B_c))
 _GLOBAL = dict(seed=((), torch.int32), episode=((), torch.int64), mt_state=((_lib.SEED_DEPTH, 2, 624), torch.int32),
@@ -53,10 +53,14 @@ class RaggedVectorEnv:
         stride = int(seed_stride) if seed_stride is not None else B
         self.seed_stride, self.env_index_base = stride, int(env_index_base)
         extra = dict(device=device, _library=_library) if _library is not None else dict(device=device)
+        # every class must be one the engine admits before anything is allocated
+        self._L = engine_library(self.device, _library)
+        for (b, n, m), ckw in zip(self.sizes, self.class_kwargs):
+            cfg = make_config(env_id, b, normalize_kwargs(env_id, n, m, **ckw))
+            _lib.check(self._L, self._L.ge_get_layout(C.byref(cfg), C.byref(_lib.GeLayout())), "ge_get_layout")
         probe = VectorGraphEnv(env_id, 1, self.sizes[0][1], self.sizes[0][2], _defer_create=True, **extra, **self.class_kwargs[0])
         F, Fe, edge_env = probe.F, probe.Fe, env_id in ("SteinerTree-v0", "MulticastRouting-v0")
         self.edge_env = edge_env
-        self._L = probe._L
         dev = self.device
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
         Nn = sum(b * n for b, n, _ in self.sizes)

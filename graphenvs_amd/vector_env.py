@@ -78,6 +78,27 @@ def normalize_kwargs(env_id, n_nodes, n_edges=-1, **kwargs):
     return kw
 
 
+def engine_library(device, _library=None):
+    """the HIP library for a GPU device (no CPU path), or the handle a test passes in"""
+    if _library is not None:
+        return _library  # CPU sanitizer harness (tests/emu), host memory
+    if torch.device(device).type != "cuda":
+        raise RuntimeError("graphenvs_amd runs on a ROCm GPU only (device='cuda'); there is no CPU path")
+    if not torch.cuda.is_available():
+        raise RuntimeError("graphenvs_amd: no GPU visible to torch (torch.cuda.is_available() is False)")
+    return _lib.load()
+
+
+def make_config(env_id, num_envs, kw, autoreset_mode=1, env_index_base=0, seed_stride=None, node_id_base=0, edge_row_stride=0):
+    """ge_config of include/graphenvs.h from normalize_kwargs() output: what ge_get_layout and ge_create are asked with"""
+    return _lib.GeConfig(
+        _lib.ENV_TYPES[env_id], int(num_envs), kw["n_nodes"], kw["n_edges"], int(bool(kw.get("weighted", False))),
+        int(kw.get("parenting", -1)), int(kw.get("n_dests", kw.get("target_count", kw.get("n_products", 0)))), int(bool(kw.get("spatial", False))),
+        int(bool(kw.get("is_eval_env", False))), int(autoreset_mode), float(kw.get("n_choices", -1)),
+        int(env_index_base), int(seed_stride if seed_stride is not None else num_envs), int(node_id_base), int(edge_row_stride),
+        float(kw["max_distance"]) if env_id == "DistributionCenter-v0" else 0.0, *kw.get("_dt_window", (0.0, 0.0)))
+
+
 class GraphBatch(SimpleNamespace):
     """PyG ``Batch``-shaped view of the engine's observation slabs (x, edge_index, edge_attr, batch, ptr).
     Tensors alias engine memory and are valid until the next step()/reset(); ``to_pyg()`` upgrades to a
@@ -160,24 +181,13 @@ class VectorGraphEnv(_VectorBase):
         assert autoreset in (True, False, "same_step", "next_step"), autoreset
         self.autoreset_mode = 2 if autoreset == "next_step" else int(bool(autoreset))
         self.autoreset = bool(autoreset)
-        if _library is None:
-            if self.device.type != "cuda":
-                raise RuntimeError("graphenvs_amd runs on a ROCm GPU only (device='cuda'); there is no CPU path")
-            if not torch.cuda.is_available():
-                raise RuntimeError("graphenvs_amd: no GPU visible to torch (torch.cuda.is_available() is False)")
-            self._L = _lib.load()
-        else:
-            self._L = _library  # CPU sanitizer harness (tests/emu), host memory
+        self._L = engine_library(self.device, _library)
         kw = self.kwargs
         self.n, self.m = kw["n_nodes"], kw["n_edges"]
         self.seed_stride = int(seed_stride) if seed_stride is not None else self.num_envs
         self.env_index_base = int(env_index_base)
-        self.cfg = _lib.GeConfig(
-            _lib.ENV_TYPES[env_id], self.num_envs, self.n, self.m, int(bool(kw.get("weighted", False))),
-            int(kw.get("parenting", -1)), int(kw.get("n_dests", kw.get("target_count", kw.get("n_products", 0)))), int(bool(kw.get("spatial", False))),
-            int(bool(kw.get("is_eval_env", False))), self.autoreset_mode, float(kw.get("n_choices", -1)),
-            self.env_index_base, self.seed_stride, int(node_id_base), int(edge_row_stride),
-            float(kw["max_distance"]) if env_id == "DistributionCenter-v0" else 0.0, *kw.get("_dt_window", (0.0, 0.0)))
+        self.cfg = make_config(env_id, self.num_envs, kw, self.autoreset_mode, self.env_index_base, self.seed_stride,
+                               node_id_base, edge_row_stride)
         lay = _lib.GeLayout()
         _lib.check(self._L, self._L.ge_get_layout(C.byref(self.cfg), C.byref(lay)), "ge_get_layout")
         self.layout = lay

@@ -4,7 +4,7 @@ Imports the real reference from /root/reference through oracle/refshim.py, rolls
 in-scope env with two deterministic policies and writes compact fixtures to
 tests/golden/<case>.npz.  A fixture is data only: inputs (env id, kwargs, seeds, actions) and
 the reference's outputs (obs, masks, rewards, done flags, info values).  No reference source
-is stored.  Re-run:  python oracle/gen_golden.py [--only NAME]
+is stored.  Re-run:  python oracle/gen_golden.py [--only NAME[,NAME...]]
 """
 import argparse
 import hashlib
@@ -136,7 +136,42 @@ CASES = {
     # differs under glibc 2.35).  The engine and the checker multiply, so rewards of such an edge agree to 1 ulp of float64, not exactly:
     # the replay compares the rewards of spatial TSP within north_star's 1e-6 and reports how many were inexact
     "tsp_n12_m30_p1_spatial_pow2": ("TSP-v0", dict(n_nodes=12, n_edges=30, parenting=1, spatial=True), [42, 217, 277]),
+    # above 600 nodes, up to the largest graphs the engine admits (tests/test_geometry_limits.py finds that edge: n = 794 at m = 3 n,
+    # n = 768 at the m = 4 n of TSP, whose reset would reject about every graph of m = 3 n for a node of degree 1): node sets of 10 to
+    # 13 words, the generic feature kernel at its lowest wave counts.  One seed each; few destinations keep the edge-action episodes
+    # (and their packed masks) short
+    "sp_n794_m2382_eval": ("ShortestPath-v0", dict(n_nodes=794, n_edges=2382, is_eval_env=True), [0]),
+    "sp_n705_m2000": ("ShortestPath-v0", dict(n_nodes=705, n_edges=2000), [0]),
+    "lp_n700_m2100_p2": ("LongestPath-v0", dict(n_nodes=700, n_edges=2100, parenting=2), [0]),
+    "lp_n793_m2379_p2": ("LongestPath-v0", dict(n_nodes=793, n_edges=2379, parenting=2), [0]),
+    "tsp_n768_m3072_p2": ("TSP-v0", dict(n_nodes=768, n_edges=3072, parenting=2), [0]),
+    "tsp_n615_m2100_p1_spatial": ("TSP-v0", dict(n_nodes=615, n_edges=2100, parenting=1, spatial=True), [0]),  # (larger ones pass the size of tsp_n128_complete_p1.npz)
+    "ds_n720_m2160_p1": ("DensestSubgraph-v0", dict(n_nodes=720, n_edges=2160, parenting=1), [0]),
+    "mis_n790_m2370": ("MaxIndependentSet-v0", dict(n_nodes=790, n_edges=2370), [0]),
+    "dc_n680_m2040_p2": ("DistributionCenter-v0", dict(n_nodes=680, n_edges=2040), [0]),
+    "mc_n750_m2250_p4_d3": ("MulticastRouting-v0", dict(n_nodes=750, n_edges=2250, n_dests=3), [0]),
+    "ppd_n640_m1920_p2": ("PerishableProductDelivery-v0", dict(n_nodes=640, n_edges=1920, n_products=2, parenting=1), [0]),
+    "st_n792_m2376_d3": ("SteinerTree-v0", dict(n_nodes=792, n_edges=2376, n_dests=3), [0]),
 }
+
+# constructor calls whose outcome in the reference (built, or the exception its asserts raise) is recorded once in
+# tests/golden/constructor_refusals.json (--constructors): every parenting value around each env's range, the weighted / spatial /
+# n_products asserts and a kwarg an env does not take.  n_nodes = 12, n_edges = 30 throughout
+_G = dict(n_nodes=12, n_edges=30)
+CONSTRUCTORS = (
+    [("ShortestPath-v0", dict(_G, **kw)) for kw in (dict(), dict(parenting=-1), dict(parenting=0), dict(parenting=1), dict(weighted=False))]
+    + [("LongestPath-v0", dict(_G, **kw)) for kw in (dict(),) + tuple(dict(parenting=p) for p in (-1, 0, 1, 2, 3, 4))]
+    + [("SteinerTree-v0", dict(_G, **kw)) for kw in (dict(), dict(parenting=-1), dict(parenting=1), dict(parenting=2), dict(n_dests=5))]
+    + [("TSP-v0", dict(_G, **kw)) for kw in (dict(),) + tuple(dict(parenting=p) for p in (-1, 0, 1, 2, 3))
+       + (dict(parenting=1, spatial=True), dict(parenting=1, spatial=True, weighted=False), dict(parenting=2, weighted=False))]
+    + [("DensestSubgraph-v0", dict(_G, **kw)) for kw in (dict(),) + tuple(dict(parenting=p) for p in (-1, 0, 1, 2))
+       + (dict(parenting=1, weighted=True), dict(parenting=0, weighted=True), dict(parenting=1, weighted=False))]
+    + [("MaxIndependentSet-v0", dict(_G, **kw)) for kw in (dict(), dict(weighted=False), dict(parenting=1))]
+    + [("MulticastRouting-v0", dict(_G, **kw)) for kw in (dict(),) + tuple(dict(parenting=p) for p in (-1, 0, 1, 2, 3, 4, 5))]
+    + [("DistributionCenter-v0", dict(_G, **kw)) for kw in (dict(),) + tuple(dict(parenting=p) for p in (-1, 0, 1, 2, 3))]
+    + [("PerishableProductDelivery-v0", dict(_G, **kw)) for kw in (dict(),) + tuple(dict(parenting=p) for p in (-1, 0, 1, 2))
+       + tuple(dict(parenting=1, n_products=k) for k in (1, 5, 6, 7)) + (dict(parenting=2, n_products=6),)]
+)
 
 POLICIES = ("first", "rand")
 
@@ -253,14 +288,35 @@ def build_case(gym, name):
     return out
 
 
+def record_constructors(gym):
+    """data only: the (env id, kwargs) of CONSTRUCTORS and, for each, whether the reference's constructor raised and with what type"""
+    rows = []
+    for env_id, kwargs in CONSTRUCTORS:
+        try:
+            gym.make(env_id, **kwargs)
+            raised = None
+        except (AssertionError, ValueError, TypeError) as e:
+            raised = type(e).__name__
+        rows.append(dict(env_id=env_id, kwargs=kwargs, raised=raised is not None, error=raised))
+    path = os.path.join(OUT, "constructor_refusals.json")
+    with open(path, "w") as f:
+        json.dump(dict(source="reference teshnizi/GraphEnvs graph-envs 0.0.54 via oracle/refshim.py", cases=rows), f, indent=1)
+        f.write("\n")
+    print(f"constructor_refusals.json: {len(rows)} calls, {sum(r['raised'] for r in rows)} refused")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default=None)
+    ap.add_argument("--constructors", action="store_true", help="record the constructor outcomes only")
     args = ap.parse_args()
     gym, _ = refshim.load_reference()
     os.makedirs(OUT, exist_ok=True)
+    if args.constructors:
+        record_constructors(gym)
+        return
     for name in CASES:
-        if args.only and args.only != name:
+        if args.only and name not in args.only.split(","):
             continue
         t0 = time.time()
         data = build_case(gym, name)

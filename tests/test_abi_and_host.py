@@ -94,6 +94,71 @@ def test_host_asserts_match_reference_constructors():
     assert utils.get_env_info("MulticastRouting-v0") == (9, 2, "edge") and utils.get_env_info("PerishableProductDelivery-v0") == (21, 1, "node")
 
 
+def _recorded_constructors():
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "constructor_refusals.json")) as f:
+        return [(c["env_id"], c["kwargs"], c["raised"], c["error"]) for c in json.load(f)["cases"]]
+
+
+@pytest.fixture(scope="module")
+def emu():
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tests", "emu"))
+    import build_emu
+    return build_emu.load()
+
+
+@pytest.mark.parametrize("env_id,kwargs,raised,error", _recorded_constructors(),
+                         ids=[f"{e.split('-')[0]}-{'-'.join(f'{k}={v}' for k, v in kw.items() if k not in ('n_nodes', 'n_edges')) or 'defaults'}"
+                              for e, kw, _, _ in _recorded_constructors()])
+def test_constructors_refuse_exactly_what_the_reference_refuses(emu, env_id, kwargs, raised, error):
+    """tests/golden/constructor_refusals.json: constructor calls and whether the reference's constructor raised (recorded once by
+    oracle/gen_golden.py --constructors).  ge.make and ge.make_vec raise the same exception type for the refused ones and build an
+    engine for the rest; derive() in ge_api.hip, asked directly past the host's asserts, answers GE_E_BADARG for the same set."""
+    makers = [lambda: ge.make(env_id, device="cpu", _library=emu, **kwargs),
+              lambda: ge.make_vec(env_id, 3, device="cpu", _library=emu, **kwargs)]
+    for make in makers:
+        if raised:
+            with pytest.raises({"AssertionError": AssertionError, "ValueError": ValueError, "TypeError": TypeError}[error]):
+                make()
+        else:
+            env = make()
+            env.close() if hasattr(env, "close") else None
+    if error == "TypeError":  # a kwarg the env does not take: nothing to put into a ge_config
+        return
+    kw = dict(ge.vector_env._DEFAULTS[env_id], **kwargs)
+    if env_id == "DistributionCenter-v0":
+        kw["target_count"] = kw["n_nodes"] // 5
+    if env_id == "PerishableProductDelivery-v0":
+        kw["_dt_window"] = (0.5, 1.5)
+    cfg = ge.vector_env.make_config(env_id, 3, kw)
+    rc = emu.ge_get_layout(C.byref(cfg), C.byref(_lib.GeLayout()))
+    assert rc == (-1 if raised else 0), (rc, emu.ge_last_error())
+    assert not raised or emu.ge_last_error()
+
+
+# refusals of the engine's own (DESIGN.md, "Deliberate differences"): calls the reference's constructor accepts and then cannot
+# serve -- its reset would not return, or raises later.  (kwargs, what the host raises, the engine's return code in the message)
+OWN_REFUSALS = [
+    ("ShortestPath-v0", dict(n_nodes=140, n_edges=147), RuntimeError, r"code -2\).*probability"),       # too disconnected to sample
+    ("TSP-v0", dict(n_nodes=200, n_edges=380, parenting=1), RuntimeError, r"code -2\).*degree-1"),
+    ("ShortestPath-v0", dict(n_nodes=12, n_edges=10), RuntimeError, r"code -1\).*no connected graph"),
+    ("SteinerTree-v0", dict(n_nodes=12, n_edges=30, n_dests=0), RuntimeError, r"code -1\).*n_dests"),
+    ("SteinerTree-v0", dict(n_nodes=12, n_edges=30, n_dests=12), RuntimeError, r"code -1\).*n_dests"),
+    ("MulticastRouting-v0", dict(n_nodes=12, n_edges=30, n_dests=12), RuntimeError, r"code -1\).*n_dests"),
+    ("PerishableProductDelivery-v0", dict(n_nodes=8, n_edges=12, n_products=5, parenting=1), RuntimeError, r"code -1\).*2 \* n_products"),
+    ("PerishableProductDelivery-v0", dict(n_nodes=12, n_edges=30, parenting=1, delivery_time=2.0), AssertionError, "delivery_time"),
+]
+
+
+@pytest.mark.parametrize("env_id,kwargs,exc,match", OWN_REFUSALS)
+def test_refusals_of_the_engine_alone_carry_their_code(emu, env_id, kwargs, exc, match):
+    for make in (lambda: ge.make(env_id, device="cpu", _library=emu, **kwargs),
+                 lambda: ge.make_vec(env_id, 3, device="cpu", _library=emu, **kwargs)):
+        with pytest.raises(exc, match=match):
+            make()
+
+
 def test_product_refuses_to_run_without_gpu():
     if torch.cuda.is_available():
         pytest.skip("GPU present")
