@@ -33,7 +33,7 @@ class RaggedVectorEnv:
     envs --, ``.t[...]``)."""
 
     def __init__(self, env_id, sizes, device="cuda", env_index_base=0, seed_stride=None, autoreset=True, _library=None, prefetch=None,
-                 **kwargs):
+                 record_actions=False, **kwargs):
         self.env_id, self.device = env_id, torch.device(device)
         # every class normalised like a uniform engine (the reference's asserts and defaults), before any device allocation
         self.class_kwargs, self.sizes = [], []
@@ -71,6 +71,9 @@ class RaggedVectorEnv:
         self.g = {k: z((B,) + shape, dt) for k, (shape, dt) in _GLOBAL.items()}
         self.g["reset_list"], self.g["reset_count"] = z((B,), torch.int32), z(((B + 255) // 256,), torch.int32)
         self.g["work_list"], self.g["work_count"] = z((B,), torch.int32), z((4,), torch.int32)
+        # where the fused policy+step launches record the actions they drew: one engine-wide array, which the engine takes from
+        # class 0's ge_buffers (include/graphenvs.h, ge_create_ragged)
+        self.g["actions_out"] = z((B,), torch.int64) if record_actions else None
         self.classes, self.slot_ptr, self._offsets = [], [0], []
         noff = eoff = slot = moff = 0
         ptr = [0]
@@ -80,8 +83,12 @@ class RaggedVectorEnv:
                          mask=self.mask_flat[moff:moff + b * A].view(b, A))
             views.update({k: self.g[k][slot:slot + b] for k in _GLOBAL})
             views.update({k: self.g[k] for k in ("reset_list", "reset_count", "work_list", "work_count")})
+            first = record_actions and slot == 0
+            if first:
+                views["actions_out"] = self.g["actions_out"]
             env = VectorGraphEnv(env_id, b, n, m, env_index_base=self.env_index_base + slot, seed_stride=stride, autoreset=autoreset,
-                                 _views=views, node_id_base=noff, edge_row_stride=Ne, _defer_create=True, prefetch=0, **extra, **ckw)
+                                 _views=views, node_id_base=noff, edge_row_stride=Ne, _defer_create=True, prefetch=0,
+                                 record_actions=first, **extra, **ckw)
             self.classes.append(env)
             self._offsets.append((noff, eoff, slot, moff, b, n, E, A))
             ptr += [noff + (i + 1) * n for i in range(b)]

@@ -155,6 +155,34 @@ def test_emulated_fused_rollout_equals_sample_then_step(emu, env_id, kw):
     assert int(a.t["episode"].sum()) > 0
 
 
+@pytest.mark.parametrize("env_id,kw", [("SteinerTree-v0", dict(n_nodes=40, n_edges=100, n_dests=5)),    # A = 200, AW = 4: all four lanes of the quad
+                                       ("SteinerTree-v0", dict(n_nodes=64, n_edges=144, n_dests=6))])   # A = 288, AW = 5: a second chunk
+def test_emulated_fused_rollout_matches_oracle_and_unfused_twin(emu, env_id, kw):
+    """the quad sampler of ge_k_step_edge over mask rows of more than one word (its cross-lane exchanges run lane after lane here:
+    tests/test_gpu_fused_rollout.py runs the same body on the GPU)"""
+    import fused_check as fc
+    import oracle
+    fc.check_fused_vs_oracle(ge, oracle, "cpu", emu, env_id, kw, 70, 40)
+
+
+@pytest.mark.parametrize("env_id,sizes,common", [
+    # the quad kernel stages rows of AW 1 / 5 / 10 with the widest stride; the last class is MST
+    ("SteinerTree-v0", [(20, 12, 30, dict(n_dests=3)), (30, 64, 144, dict(n_dests=6)), (20, 100, 300, dict(n_dests=99))], {}),
+    # thread-per-slot kernel: a slot's class-local index is not its index in the engine-wide actions_out
+    ("TSP-v0", [(20, 14, 40), (20, 20, 60)], dict(parenting=2))])
+def test_emulated_fused_rollout_of_the_multi_class_engine(emu, env_id, sizes, common):
+    import fused_check as fc
+    import oracle
+    fc.check_fused_ragged_vs_oracle(ge, oracle, "cpu", emu, env_id, sizes, common, 30)
+
+
+def test_emulated_fused_rollout_records_minus_one_for_frozen_slots(emu):
+    import fused_check as fc
+    import oracle
+    st = fc.check_fused_vs_oracle(ge, oracle, "cpu", emu, "ShortestPath-v0", dict(n_nodes=10, n_edges=20), 300, 40, autoreset=False)
+    assert st["minus_ones"] >= 2 * 300
+
+
 def test_emulated_feature_fast_path_falls_back_to_generic_when_too_deep(stress):
     """-DGE_F64_LV=3 forces the lane-per-source path to hand deep slots to the generic kernel."""
     lib = stress
