@@ -5,6 +5,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <initializer_list>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -16,18 +18,28 @@
 #include "ge_tsp_eval.h"
 #include "ge_spare.h"
 
-// Multi-class engine: size classes are grouped into LDS buckets (by n_nodes: <= 128, <= 256, <= 512, larger), and the graph kernel
-// and the generic feature kernel are launched once per bucket with the dynamic LDS -- hence the residency -- of the bucket's largest
-// class (round 2 ran every class at the occupancy of n = 512: one workgroup per CU)
+// An engine's launch geometry: filled once when the engine is created (finish_create), read by every launch, computed nowhere else.
+// The size classes of a multi-class engine are grouped into LDS buckets (by n_nodes: <= 128, <= 256, <= 512, larger), and the graph
+// kernel and the generic feature kernel are launched once per bucket with the dynamic LDS -- hence the residency -- of the bucket's
+// largest class (round 2 ran every class at the occupancy of n = 512: one workgroup per CU).  A uniform engine is ONE bucket whose
+// only class is e->P; its launches pass the bucket index -1 (no class filter in the kernels).
 #define GE_MAX_BUCKETS 4
 struct GeBucket {
   bool used;
-  int reset_lds, reset_grid;                     // graph kernel
-  int gen_lds, gen_pre_off, gen_waves, gen_grid;  // generic feature kernel (classes with n > 64)
-  bool gen_used;
-  int fb_lds, fb_pre_off;  // a bucket of classes with n <= 64 only: the generic kernel for the fast path's fallback list (slots too deep for it)
+  bool list_only;  // classes on the n <= 64 fast path only: the generic feature kernel serves that path's fallback list (slots too deep for it)
+  struct { int lds, pre, grid; } graph;             // graph kernel: dynamic LDS bytes, GeLds.pre of the launch, resident workgroups
+  struct { int lds, pre_off, threads, grid; } gen;  // generic feature kernel (list_only: grid is the whole launch)
+};
+struct GePlan {
+  int n_buckets;  // 1: uniform engine
+  GeBucket bk[GE_MAX_BUCKETS];
+  int nseed;      // seeding workgroups at the head of the queue-mode reset launch (64 queued slots each)
+  bool feat_fast;                       // a class takes the n <= 64 feature kernel (spatial TSP: float64 weights do not fit its LDS)
+  int f64_lds, f64_pre_off, feat_grid;  // that kernel's launch; feat_grid without it: resident workgroups of the generic kernel at the largest class's carve
+  GeLds inject;   // ge_inject_state runs the graph kernel on this carve (inject_carve)
 };
 static int bucket_of(int n) { return n <= 128 ? 0 : (n <= 256 ? 1 : (n <= 512 ? 2 : 3)); }
+static bool takes_generic(const GeParams &C) { return C.n > 64 || C.spatial; }  // the class's slots run the generic feature kernel, not the fast path
 
 // The kernel instantiations an engine runs, chosen once when it is created (select_kernels).  Every launch and every raise of a
 // dynamic-LDS limit takes its kernel from here, so the instantiation whose limit was raised is the one that is launched.
@@ -53,21 +65,15 @@ struct ge_engine {
   GeParams P;
   ge_config cfg;
   GeKernels k = {};
-  int reset_grid;     // workgroups of the queue-mode reset launch
-  int lds_bytes;
-  int feat_lds, feat_grid, feat_fast, gen_grid, gen_lds;  // structural-feature kernel launch geometry
+  GePlan plan = {};
   hipEvent_t ev[4];
   bool have_events = false;
-  int nseed;      // seeding workgroups at the head of the queue-mode reset launch (64 queued slots each)
   // multi-class ("ragged") engine: P is then the engine-wide block (B = all slots, global queue / seed / episode / mt_state arrays,
   // n / m / W = the widest class) and R names the device copy of the class table
   int n_classes = 0;
   GeRagged R = {};
   int aw_max;     // the widest mask row (multi-class engine: over the classes; edge-action envs: 2 m words, not a function of n)
   std::vector<GeParams> classes;  // host copy (ge_vectorize launches per class)
-  int feat64_pre_off, gen_pre_off;
-  int lds_bytes_inject;  // GeParams.nocolw engines: ge_inject_state runs the graph kernel on the full LDS carve (the injected rows need the list)
-  GeBucket bk[GE_MAX_BUCKETS] = {};
   bool loaded = false;    // the slots hold an episode (ge_reset or ge_inject_state ran)
   bool seeded = false;    // the generator-state ring is valid (ge_reset, or ge_inject_state with seeds)
   bool streams = false;   // stream_state holds the streams a regeneration left behind (ge_reset; a restored snapshot)
@@ -107,6 +113,10 @@ extern "C" const char *ge_source_hash(void) { return g_source_hash + 15; }
 static const int kMaxLds = 160 * 1024;
 static const GeInject kNoInject = {nullptr, nullptr, nullptr, nullptr, nullptr};
 static int step_blocks(int64_t B) { return (int)((B + GE_STEP_BLOCK - 1) / GE_STEP_BLOCK); }  // workgroups of GE_STEP_BLOCK slots (one queue counter each)
+// LDS bytes of the queue prefix of an engine of B slots: the kernels index it with step_blocks(B) + 2 entries
+static int prefix_bytes(int64_t B) { return (step_blocks(B) + 2) * 4; }
+// every dynamic-LDS size an engine would launch with fits a CU
+static bool carves_fit(std::initializer_list<int> bytes) { for (int b : bytes) if (b > kMaxLds) return false; return true; }
 // workgroups that stay resident at `lds` bytes each (256 CUs, at most 16 per CU), no more than one per slot
 static int resident_grid(int lds, int64_t B) {
   int per_cu = kMaxLds / (lds > 0 ? lds : 1);
@@ -140,10 +150,10 @@ static bool prunes(const GeParams &P) { return (P.env_type == GE_LONGEST_PATH ||
 
 // GeParams.nocolw engines: ge_inject_state runs the graph kernel on the full LDS carve (the injected rows need the {neighbour, code}
 // list the reset of such an engine does without)
-static int inject_lds_bytes(const GeParams &P, int queue_B) {
-  if (!P.nocolw) return P.lds.total;
+static GeLds inject_carve(const GeParams &P, int queue_B) {
+  if (!P.nocolw) return P.lds;
   GeParams Pi = P; Pi.nocolw = 0; Pi.nowsort = 0; ge_make_lds(Pi, queue_B);
-  return Pi.lds.total;
+  return Pi.lds;
 }
 
 static int derive(const ge_config *cfg, GeParams &P, int queue_B = 0) {
@@ -220,9 +230,9 @@ static int derive(const ge_config *cfg, GeParams &P, int queue_B = 0) {
   ge_tune_feat_parts(P);
   // every carve finish_create launches with, so that the layout query refuses what ge_create / ge_create_ragged would: the graph
   // kernel's (ge_inject_state included), and the two a multi-class engine lengthens by a second queue prefix behind its widest class
-  const int pre2 = (step_blocks(qB) + 2) * 4;
-  const int reset_need = P.lds.total + (P.lds.pre != 0 ? pre2 : 0), inject_need = inject_lds_bytes(P, qB);
-  if (reset_need > kMaxLds || inject_need > kMaxLds || P.ldsf.total + pre2 > kMaxLds) return fail(GE_E_TOOBIG, "per-env graph does not fit 160 KiB of LDS");
+  const int pre2 = prefix_bytes(qB);
+  if (!carves_fit({P.lds.total + (P.lds.pre != 0 ? pre2 : 0), inject_carve(P, qB).total, P.ldsf.total + pre2}))
+    return fail(GE_E_TOOBIG, "per-env graph does not fit 160 KiB of LDS");
   return GE_OK;
 }
 
@@ -323,52 +333,66 @@ static bool raise_lds(const void *kernel, size_t bytes) {
   return bytes <= 64 * 1024 || (hipError_t)GE_SET_MAX_DYN_LDS(kernel, bytes) == hipSuccess;
 }
 
-// kernels, launch geometry and LDS limits from e->P (uniform engine) or from the class table (multi-class engine); deletes e on failure
-static int finish_create(ge_engine *e, ge_engine **out) {
+// kernels, the launch plan and the LDS limits from e->P (uniform engine) or from the class table (multi-class engine)
+static int finish_create(ge_engine *e) {
   const GeParams &P = e->P;
-  const int nblk = step_blocks(P.B);
   const bool rg = e->n_classes > 0;
+  const int nblk = step_blocks(P.B), pre2 = prefix_bytes(P.B);
   GE_FOR_ENV(P.env_type, if (rg) (select_kernels<ENV, true>(e)); else (select_kernels<ENV, false>(e)));
-  // ---- graph kernel
-  int reset_lds = P.lds.total, gen_lds = P.ldsf.total, f64_body = 0;
-  bool any64 = !rg && P.n <= 64 && !P.spatial;
-  if (!rg) f64_body = ge_f64_pre_off(P.E, P.env_type == GE_TSP, nblk);
-  for (const GeParams &C : e->classes) {
-    if (C.lds.total > reset_lds) reset_lds = C.lds.total;
-    if (C.ldsf.total > gen_lds) gen_lds = C.ldsf.total;
-    if (C.n <= 64 && !C.spatial) { any64 = true; const int b = ge_f64_pre_off(C.E, C.env_type == GE_TSP, nblk); if (b > f64_body) f64_body = b; }
+  GePlan &L = e->plan;
+  // a multi-class launch keeps the queue prefix BEHIND the widest carve of the bucket's classes (a class's own carve places it for
+  // that class alone); the carve of a uniform engine holds it
+  auto behind = [&](int body, int &pre) { pre = ge_align16(body); return pre + pre2; };
+  const GeParams *first = rg ? e->classes.data() : &e->P;
+  const int n_classes = rg ? e->n_classes : 1;
+  L.n_buckets = rg ? GE_MAX_BUCKETS : 1;
+  int graph_lds = 0, gen_lds = 0;   // the largest launch of the graph kernel and of the generic feature kernel
+  int gen_body = 0, f64_body = 0;  // the largest carve of a class on the generic kernel; the fast path's item bodies
+  for (int b = 0; b < L.n_buckets; b++) {
+    GeBucket &K = L.bk[b];
+    int graph = 0, gen = 0, all = 0, waves = 1;
+    for (const GeParams *C = first; C < first + n_classes; C++) {
+      if (C->bucket != b) continue;
+      K.used = true;
+      if (C->lds.total > graph) graph = C->lds.total;
+      if (C->ldsf.total > all) all = C->ldsf.total;
+      if (takes_generic(*C)) { if (C->ldsf.total > gen) gen = C->ldsf.total; if (C->ldsf.waves > waves) waves = C->ldsf.waves; }
+      else { L.feat_fast = true; const int body = ge_f64_pre_off(C->E, C->env_type == GE_TSP, nblk); if (body > f64_body) f64_body = body; }
+    }
+    if (!K.used) continue;
+    K.list_only = gen == 0;
+    if (gen > gen_body) gen_body = gen;
+    // ---- graph kernel
+    K.graph.grid = resident_grid(graph, P.B);
+    K.graph.pre = P.lds.pre; K.graph.lds = graph;
+    if (rg && P.lds.pre != 0) K.graph.lds = behind(graph, K.graph.pre);  // (else the prefix overlays the generator state at the head of every carve)
+    if (K.graph.lds > graph_lds) graph_lds = K.graph.lds;
+    // ---- generic feature kernel: the wave count every class of the bucket can hold (a class's surplus waves do not search,
+    // ge_features_generic_env); list_only: one wave per slot (ge_make_ldsf: n <= 64), sized for the bucket's largest class
+    K.gen.threads = GE_WAVE * waves;
+    K.gen.pre_off = P.ldsf.pre; K.gen.lds = P.ldsf.total;
+    if (rg) K.gen.lds = behind(K.list_only ? all : gen, K.gen.pre_off);
+    K.gen.grid = resident_grid(K.gen.lds, P.B);
+    // (the fallback list is normally empty and a handful of slots at most: eight workgroups dispatch in less time than 64 -- the
+    // launch is on every step's critical path)
+    if (K.list_only && (rg || K.gen.grid > 8)) K.gen.grid = 8;
+    if (K.gen.lds > gen_lds) gen_lds = K.gen.lds;
   }
-  if (rg && e->P.lds.pre != 0) { e->P.lds.pre = ge_align16(reset_lds); reset_lds = e->P.lds.pre + (nblk + 2) * 4; }  // prefix behind every class's scratch
-  e->lds_bytes = reset_lds;
-  e->lds_bytes_inject = reset_lds;
-  if (!rg) e->lds_bytes_inject = inject_lds_bytes(P, P.B);
-  if (reset_lds > kMaxLds || gen_lds > kMaxLds || e->lds_bytes_inject > kMaxLds) { delete e; return fail(GE_E_TOOBIG, "per-env graph does not fit 160 KiB of LDS"); }
-  e->reset_grid = resident_grid(reset_lds, P.B);
-  e->nseed = (e->reset_grid + 63) / 64;  // one seeding workgroup per 64 regenerating workgroups: the usual queue fits one round of both
-  // (ge_inject_state on a nocolw engine launches the same kernel on the full carve: the larger of the two sizes)
-  if (!raise_lds((const void *)e->k.reset, reset_lds > e->lds_bytes_inject ? reset_lds : e->lds_bytes_inject)) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the reset kernel"); }
+  if (!rg) L.inject = inject_carve(P, P.B);  // (ge_inject_state is not built for the multi-class engine)
+  if (!carves_fit({graph_lds, L.inject.total, gen_lds})) return fail(GE_E_TOOBIG, "per-env graph does not fit 160 KiB of LDS");
+  L.nseed = (resident_grid(graph_lds, P.B) + 63) / 64;  // one seeding workgroup per 64 regenerating workgroups: the usual queue fits one round of both
+  if (!raise_lds((const void *)e->k.reset, graph_lds > L.inject.total ? graph_lds : L.inject.total)) return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the reset kernel");
   // ---- step kernel: the quad-per-slot stage of the edge-action envs (mask rows + node sets of 256 slots) passes 64 KB; the
   // thread-per-slot stage (one node set per slot of the workgroup) would above 2 048 nodes
-  if (!raise_lds((const void *)e->k.step[0], e->k.step_lds) || !raise_lds((const void *)e->k.step[1], e->k.step_lds)) {
-    const bool quad = e->k.step_quad;
-    delete e;
-    return fail(GE_E_LAUNCH, quad ? "cannot raise the dynamic LDS limit of the edge step kernel" : "cannot raise the dynamic LDS limit of the step kernel");
-  }
-  // ---- feature kernels
-  e->feat_fast = any64 ? 1 : 0;  // (spatial TSP: float64 weights do not fit the fast path's LDS)
-  e->feat64_pre_off = ge_align16(f64_body);  // the item bodies (the queue prefix overlays them), then the tail {item slots, overflow flag}
-  e->feat_lds = e->feat_fast ? e->feat64_pre_off + GE_F64_ITEMS * 4 * 4 + 16 : gen_lds;
-  e->gen_lds = gen_lds;
-  e->gen_pre_off = P.ldsf.pre;
-  if (rg) { e->gen_pre_off = ge_align16(gen_lds); e->gen_lds = e->gen_pre_off + (nblk + 2) * 4; }
-  if (e->feat_lds > kMaxLds || e->gen_lds > kMaxLds) { delete e; return fail(GE_E_TOOBIG, "feature kernel does not fit LDS"); }
-  for (const GeBucket &K : e->bk)  // a bucket of classes with n <= 64 only launches the generic kernel for the fast path's fallback list
-    if (K.used && !K.gen_used && !raise_lds((const void *)e->k.features, K.fb_lds)) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the feature kernel"); }
-  if (!raise_lds((const void *)e->k.features, e->gen_lds)) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the feature kernel"); }
-  if (e->feat_fast && !raise_lds((const void *)e->k.features64, e->feat_lds)) { delete e; return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the n<=64 feature kernel"); }
-  e->gen_grid = resident_grid(e->gen_lds, P.B);
-  e->feat_grid = resident_grid(e->feat_lds, P.B);
-  *out = e;
+  if (!raise_lds((const void *)e->k.step[0], e->k.step_lds) || !raise_lds((const void *)e->k.step[1], e->k.step_lds))
+    return fail(GE_E_LAUNCH, e->k.step_quad ? "cannot raise the dynamic LDS limit of the edge step kernel" : "cannot raise the dynamic LDS limit of the step kernel");
+  // ---- n <= 64 feature kernel: the item bodies (the queue prefix overlays them), then the tail {item slots, overflow flag}
+  L.f64_pre_off = ge_align16(f64_body);
+  L.f64_lds = L.feat_fast ? L.f64_pre_off + GE_F64_ITEMS * 4 * 4 + 16 : 0;
+  if (!carves_fit({L.f64_lds})) return fail(GE_E_TOOBIG, "feature kernel does not fit LDS");
+  if (!raise_lds((const void *)e->k.features, gen_lds)) return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the feature kernel");
+  if (L.feat_fast && !raise_lds((const void *)e->k.features64, L.f64_lds)) return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the n<=64 feature kernel");
+  L.feat_grid = resident_grid(L.feat_fast ? L.f64_lds : gen_body, P.B);
   return GE_OK;
 }
 
@@ -380,10 +404,12 @@ extern "C" int ge_create(const ge_config *cfg, const ge_buffers *bufs, ge_engine
   rc = check_buffers(P, bufs);
   if (rc != GE_OK) return rc;
   P.buf = *bufs;
-  ge_engine *e = new (std::nothrow) ge_engine();
+  std::unique_ptr<ge_engine> e(new (std::nothrow) ge_engine());
   if (!e) return fail(GE_E_BADARG, "out of host memory");
   e->P = P; e->cfg = *cfg; e->aw_max = P.AW;
-  return finish_create(e, out);
+  rc = finish_create(e.get());
+  if (rc == GE_OK) *out = e.release();
+  return rc;
 }
 
 extern "C" int64_t ge_ragged_table_bytes(int32_t n_classes) { return (int64_t)sizeof(GeParams) * (n_classes > 0 ? n_classes : 0); }
@@ -395,7 +421,7 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
   int64_t total = 0;
   for (int c = 0; c < n_classes; c++) total += cfgs[c].num_envs;
   if (total > 8192 * GE_STEP_BLOCK) return fail(GE_E_TOOBIG, "num_envs > 2M per engine");
-  ge_engine *e = new (std::nothrow) ge_engine();
+  std::unique_ptr<ge_engine> e(new (std::nothrow) ge_engine());
   if (!e) return fail(GE_E_BADARG, "out of host memory");
   e->classes.resize(n_classes);
   std::vector<int32_t> start(n_classes + 1, 0), cls_of((size_t)total);
@@ -416,7 +442,7 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
     if (rc == GE_OK && (bufs[c].reset_list != bufs[0].reset_list || bufs[c].reset_count != bufs[0].reset_count || bufs[c].work_list != bufs[0].work_list ||
                         bufs[c].work_count != bufs[0].work_count || bufs[c].slot_rec != bufs[0].slot_rec + 2 * (int64_t)start[c]))
       rc = fail(GE_E_BADARG, "reset_list, reset_count, work_list and work_count are engine-wide (the same pointers in every class), and slot_rec of class c starts at its first global slot");
-    if (rc != GE_OK) { delete e; return rc; }
+    if (rc != GE_OK) return rc;
     C.buf = bufs[c];
     start[c + 1] = start[c] + cfgs[c].num_envs;
     for (int i = start[c]; i < start[c + 1]; i++) cls_of[(size_t)i] = c;
@@ -427,40 +453,21 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
   // above GE_MAXW words, and then every class needs its prune_scratch (ge_layout reports none for a class that would fit registers)
   if (prunes(e->classes[widest]) && e->classes[widest].W > GE_MAXW)
     for (int c = 0; c < n_classes; c++)
-      if (!bufs[c].prune_scratch) { delete e; return fail(GE_E_BADARG, "parenting >= 2 with a class above 512 nodes runs the residual-graph walks in memory for every class: each class needs prune_scratch ([B_c, 4, W_c] uint64)"); }
-  // one launch geometry of the generic feature kernel per LDS bucket: the wave count every class of the bucket can hold -- two
-  // workgroups per CU where that leaves at least four waves, else one
-  const int nblk_all = step_blocks(total);
+      if (!bufs[c].prune_scratch) return fail(GE_E_BADARG, "parenting >= 2 with a class above 512 nodes runs the residual-graph walks in memory for every class: each class needs prune_scratch ([B_c, 4, W_c] uint64)");
+  // the classes of an LDS bucket share one launch of the generic feature kernel (the plan: finish_create).  Every class takes the
+  // wave count it would choose as a uniform engine -- two workgroups per CU where that leaves at least four waves, else one; if the
+  // bucket's widest allocation then leaves room for ONE workgroup per CU only, the smaller classes are re-derived for the whole CU
+  // (up to 16 waves: idle LDS otherwise)
   for (int b = 0; b < GE_MAX_BUCKETS; b++) {
-    // every class takes the wave count it would choose as a uniform engine; if the bucket's widest allocation then leaves room for
-    // ONE workgroup per CU only, the smaller classes are re-derived for the whole CU (up to 16 waves: idle LDS otherwise).  The
-    // launch has the threads of the largest count; a class's surplus waves do not search (ge_features_generic_env)
-    int waves = 1; bool any = false, anygen = false;
-    GeBucket &K = e->bk[b];
     for (int pass = 0; pass < 2; pass++) {
-      waves = 1; K.gen_lds = 0; K.reset_lds = 0;
+      int gen_lds = 0;
       for (GeParams &C : e->classes) if (bucket_of(C.n) == b) {
-        any = true;
         C.bucket = b;
         if (pass == 0) ge_make_ldsf(C, (int)total); else ge_make_ldsf(C, (int)total, 0, 160 * 1024 - 2048);
         ge_tune_feat_parts(C);
-        if (C.lds.total > K.reset_lds) K.reset_lds = C.lds.total;
-        if (C.n > 64 || C.spatial) { anygen = true; if (C.ldsf.total > K.gen_lds) K.gen_lds = C.ldsf.total; if (C.ldsf.waves > waves) waves = C.ldsf.waves; }  // (spatial TSP: no n <= 64 fast path)
+        if (takes_generic(C) && C.ldsf.total > gen_lds) gen_lds = C.ldsf.total;
       }
-      if (2 * (K.gen_lds + (nblk_all + 2) * 4) <= kMaxLds) break;  // two workgroups per CU: the classes keep their own choice
-    }
-    K.used = any; K.gen_used = anygen; K.gen_waves = waves;
-    if (!any) continue;
-    if (!anygen) {  // one wave per slot (ge_make_ldsf: n <= 64), sized for the bucket's largest class
-      int fb = 0;
-      for (const GeParams &C : e->classes) if (C.bucket == b && C.ldsf.total > fb) fb = C.ldsf.total;
-      K.fb_pre_off = ge_align16(fb); K.fb_lds = K.fb_pre_off + (nblk_all + 2) * 4;  // (its LDS limit: finish_create, with the other kernels')
-    }
-    if (K.reset_lds < GE_SEED_LDS_BYTES) K.reset_lds = GE_SEED_LDS_BYTES;
-    K.reset_grid = resident_grid(K.reset_lds, total);
-    if (anygen) {
-      K.gen_pre_off = ge_align16(K.gen_lds); K.gen_lds = K.gen_pre_off + (nblk_all + 2) * 4;
-      K.gen_grid = resident_grid(K.gen_lds, total);
+      if (2 * (gen_lds + prefix_bytes(total)) <= kMaxLds) break;  // two workgroups per CU: the classes keep their own choice
     }
   }
   // engine-wide block: the widest class's geometry (LDS stage of the step kernel), all slots, the global arrays of class 0
@@ -476,12 +483,14 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
   if (hipMemcpy(class_table, e->classes.data(), sizeof(GeParams) * (size_t)n_classes, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(slot_class, cls_of.data(), sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(class_start, start.data(), sizeof(int32_t) * (size_t)(n_classes + 1), hipMemcpyHostToDevice) != hipSuccess) {
-    delete e; return fail(GE_E_LAUNCH, "cannot copy the class table to the device");
+    return fail(GE_E_LAUNCH, "cannot copy the class table to the device");
   }
   e->R.classes = (const GeParams *)class_table; e->R.slot_class = slot_class; e->R.class_start = class_start; e->R.n_classes = n_classes;
   e->R.f64_tsp_e = 0;
   for (const GeParams &C : e->classes) if (C.env_type == GE_TSP && C.n <= 64 && C.E > e->R.f64_tsp_e) e->R.f64_tsp_e = C.E;
-  return finish_create(e, out);
+  const int rc = finish_create(e.get());
+  if (rc == GE_OK) *out = e.release();
+  return rc;
 }
 
 // the per-slot slabs an image must hold for this (sub-)engine
@@ -577,64 +586,49 @@ static int launch_seed(ge_engine *e, const uint32_t *seeds, int jlo, void *strea
 
 // V: the engine (e->P) or its spare-image view (e->PS); VR: the matching class table
 static int launch_combine(ge_engine *e, const GeParams &V, const GeRagged &VR, GeRun run, bool small, void *stream) {
-  size_t lds = (size_t)(step_blocks(V.B) + 2) * 4;
   int64_t items = (int64_t)(run.items == GE_ITEMS_ALL ? V.B : (small ? 64 : 4096)) * V.n;
   int grid = (int)((items + 255) / 256); if (grid > 8192) grid = 8192;
-  GE_LAUNCH(e->k.feat_combine, grid, 256, lds, stream, V, VR, run);
+  GE_LAUNCH(e->k.feat_combine, grid, 256, prefix_bytes(V.B), stream, V, VR, run);
   return check_launch("feature combine kernel");
 }
 
+// a launch over every slot spreads to four times the resident grid, one workgroup per slot at most; a queue launch strides over its list
+static int spread(int grid, int B, bool queue) { return queue ? grid : (B < grid * 4 ? B : grid * 4); }
+
 // `small`: the queue is expected to be short (the in-place regenerations of an engine with spares): a fraction of the grid
+static int fast_grid(const ge_engine *e, int B, bool queue, bool small) {
+  const int g = spread(e->plan.feat_grid, B, queue);
+  return small && g > 64 ? 64 : g;
+}
+
+// workgroups of the generic feature kernel's launch for bucket K.  With the fast path in front (plan.feat_fast) the launch takes
+// the fallback list: every slot of a class with n > 64, or -- K.list_only -- the rare slots too deep for the fast path
+static int generic_grid(const ge_engine *e, const GeBucket &K, const GeParams &V, GeRun run, bool small) {
+  const bool queue = run.items == GE_ITEMS_QUEUE, list = e->plan.feat_fast;
+  if (K.list_only) return K.gen.grid;
+  int64_t want = list ? (int64_t)K.gen.grid * (queue ? 1 : 4) : fast_grid(e, V.B, queue, small);
+  want *= ge_feat_workgroups(V.feat_parts);
+  if (!list && queue && !run.refill && want > 4608) want = 4608;  // the list is short, workgroups stride over it
+  if (small && want > 288) want = 288;
+  return want > 65535 * 16 ? 65535 * 16 : (int)want;
+}
+
 static int launch_features(ge_engine *e, const GeParams &V, const GeRagged &VR, GeRun run, bool small, void *stream) {
+  const GePlan &L = e->plan;
+  const GeRun rest = L.feat_fast ? as_list(run) : run;  // behind the fast path: its fallback list
   int rc = GE_OK;
-  const bool rg = e->n_classes > 0, queue = run.items == GE_ITEMS_QUEUE;
-  int fgrid = queue ? e->feat_grid : (V.B < e->feat_grid * 4 ? V.B : e->feat_grid * 4);
-  if (small && fgrid > 64) fgrid = 64;
-  const int gen_threads = GE_WAVE * (rg ? e->classes[0].ldsf.waves : V.ldsf.waves);
-  if (e->feat_fast) {
-    GE_LAUNCH(e->k.features64, fgrid, GE_F64_THREADS, e->feat_lds, stream, V, VR, run, e->feat64_pre_off);
+  if (L.feat_fast) {
+    GE_LAUNCH(e->k.features64, fast_grid(e, V.B, run.items == GE_ITEMS_QUEUE, small), GE_F64_THREADS, L.f64_lds, stream, V, VR, run, L.f64_pre_off);
     rc = check_launch("feature kernel (n <= 64)");
-    if (rc != GE_OK) return rc;
-    // the fast path's fallback list (normally empty); multi-class engine: every slot of a class with n > 64, feat_parts workgroups each
-    if (rg) {
-      for (int b = 0; b < GE_MAX_BUCKETS && rc == GE_OK; b++) {  // one launch per LDS bucket
-        const GeBucket &K = e->bk[b];
-        if (!K.used) continue;
-        if (!K.gen_used) {  // classes with n <= 64 only: the list holds the rare slots too deep for the fast path (eight workgroups, as in a uniform engine)
-          GE_LAUNCH(e->k.features, 8, GE_WAVE, K.fb_lds, stream, V, VR, as_list(run), K.fb_pre_off, b);
-          rc = check_launch("feature kernel (fallback list)");
-          continue;
-        }
-        int64_t want = (int64_t)K.gen_grid * ge_feat_workgroups(V.feat_parts) * (queue ? 1 : 4);
-        if (small && want > 288) want = 288;
-        if (want > 65535 * 16) want = 65535 * 16;
-        GE_LAUNCH(e->k.features, (int)want, GE_WAVE * K.gen_waves, K.gen_lds, stream, V, VR, as_list(run), K.gen_pre_off, b);
-        rc = check_launch("feature kernel (list)");
-      }
-      return (rc == GE_OK && V.feat_parts > 1) ? launch_combine(e, V, VR, as_list(run), small, stream) : rc;
-    }
-    int g2 = e->gen_grid < 8 ? e->gen_grid : 8;  // (the list is normally empty and a handful of slots at most: eight workgroups dispatch in less time than 64 -- the launch is on every step's critical path)
-    GE_LAUNCH(e->k.features, g2, gen_threads, e->gen_lds, stream, V, VR, as_list(run), e->gen_pre_off, -1);
-    return check_launch("feature kernel (fallback list)");
   }
-  {
-    int64_t want = (int64_t)fgrid * ge_feat_workgroups(V.feat_parts);
-    if (queue && !run.refill && want > 4608) want = 4608;  // the list is short, workgroups stride over it
-    if (small && want > 288) want = 288;
-    if (want > 65535 * 16) want = 65535 * 16;
-    if (rg) {  // (no class with n <= 64: every slot takes the generic kernel) one launch per LDS bucket
-      for (int b = 0; b < GE_MAX_BUCKETS && rc == GE_OK; b++) {
-        const GeBucket &K = e->bk[b];
-        if (!K.gen_used) continue;
-        GE_LAUNCH(e->k.features, (int)want, GE_WAVE * K.gen_waves, K.gen_lds, stream, V, VR, run, K.gen_pre_off, b);
-        rc = check_launch("feature kernel");
-      }
-    }
-    else GE_LAUNCH(e->k.features, (int)want, gen_threads, e->gen_lds, stream, V, VR, run, e->gen_pre_off, -1);
+  for (int b = 0; b < L.n_buckets && rc == GE_OK; b++) {  // one launch per LDS bucket
+    const GeBucket &K = L.bk[b];
+    if (!K.used) continue;
+    GE_LAUNCH(e->k.features, generic_grid(e, K, V, run, small), K.gen.threads, K.gen.lds, stream, V, VR, rest, K.gen.pre_off, e->n_classes > 0 ? b : -1);
+    rc = check_launch(L.feat_fast ? "feature kernel (fallback list)" : "feature kernel");
   }
-  rc = check_launch("feature kernel");
   if (rc != GE_OK || V.feat_parts == 1) return rc;
-  return launch_combine(e, V, VR, run, small, stream);
+  return launch_combine(e, V, VR, rest, small, stream);
 }
 
 // is_eval_env baselines that are sequential programs (ge_tsp_eval.h: TSP Christofides, MaxIndependentSet clique removal, SteinerTree
@@ -642,21 +636,21 @@ static int launch_features(ge_engine *e, const GeParams &V, const GeRagged &VR, 
 // finds its class and runs on that class's eval_scratch (VR: the live or the spare class table)
 static int launch_seq_baseline(ge_engine *e, const GeParams &P, const GeRagged &VR, int queue, void *stream) {
   const uint64_t slot_bytes = e->n_classes > 0 ? 0 : eval_slot_bytes(P);
-  const int nblk = step_blocks(P.B);
+  const int pre = prefix_bytes(P.B);
   int g = (P.B + GE_TSP_EVAL_THREADS - 1) / GE_TSP_EVAL_THREADS; if (g > 4096) g = 4096;  // one thread per item
   if (P.env_type == GE_MAX_INDEPENDENT_SET) {
-    GE_LAUNCH(e->k.mis_baseline, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+    GE_LAUNCH(e->k.mis_baseline, g, GE_TSP_EVAL_THREADS, pre, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
     return check_launch("MaxIndependentSet baseline kernel");
   }
   if (P.env_type == GE_STEINER_TREE) {
-    GE_LAUNCH(e->k.steiner_baseline, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+    GE_LAUNCH(e->k.steiner_baseline, g, GE_TSP_EVAL_THREADS, pre, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
     return check_launch("SteinerTree baseline kernel");
   }
   const int pre_off = GE_WAVE * P.W * 8;  // (P.W: the widest class's in a multi-class engine)
-  GE_LAUNCH(e->k.tsp_closure, P.B < 2048 ? P.B : 2048, GE_TSP_EVAL_THREADS, pre_off + (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes, pre_off);
+  GE_LAUNCH(e->k.tsp_closure, P.B < 2048 ? P.B : 2048, GE_TSP_EVAL_THREADS, pre_off + pre, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes, pre_off);
   int rc = check_launch("TSP baseline: closure kernel");
   if (rc != GE_OK) return rc;
-  GE_LAUNCH(e->k.tsp_tour, g, GE_TSP_EVAL_THREADS, (nblk + 2) * 4, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
+  GE_LAUNCH(e->k.tsp_tour, g, GE_TSP_EVAL_THREADS, pre, stream, P, VR, queue, (uint8_t *)P.buf.eval_scratch, slot_bytes);
   return check_launch("TSP baseline: tour kernel");
 }
 
@@ -675,30 +669,22 @@ static int launch_reset(ge_engine *e, const GeParams &V, const GeRagged &VR, con
     rc = check_launch("seed kernel (next ring entry)");
     if (rc != GE_OK) return rc;
   }
-  int rgrid = e->reset_grid, nseed = e->nseed;
-  if (small && rgrid > 128) { rgrid = 128; nseed = 2; }
-  if (!queue) nseed = 0;
-  const int grid = queue ? rgrid + nseed : (V.B < e->reset_grid * 4 ? V.B : e->reset_grid * 4);
-  if (e->n_classes > 0) {
-    bool first = true;
-    for (int b = 0; b < GE_MAX_BUCKETS && rc == GE_OK; b++) {  // one launch per LDS bucket; the seeding workgroups ride in the first
-      const GeBucket &K = e->bk[b];
-      if (!K.used) continue;
-      int bg = K.reset_grid; if (small && bg > 128) bg = 128;
-      const int ns = first ? nseed : 0;
-      const int g = queue ? bg + ns : (V.B < K.reset_grid * 4 ? V.B : K.reset_grid * 4);
-      int lds = K.reset_lds;
-      GeParams V2 = V;
-      if (V.lds.pre != 0) { V2.lds.pre = ge_align16(K.reset_lds); lds = V2.lds.pre + (step_blocks(V.B) + 2) * 4; }  // queue prefix behind the bucket's scratch
-      GE_LAUNCH(e->k.reset, g, GE_RESET_THREADS, lds, stream, V2, VR, seeds, run, inj, ns, b);
-      rc = check_launch("reset kernel");
-      first = false;
-    }
-  } else if (run.inject && V.nocolw) {  // the injected rows come in the caller's order: this launch keeps the {neighbour, code} list (the full LDS carve)
-    GeParams Vi = V; Vi.nocolw = 0; Vi.nowsort = 0; ge_make_lds(Vi, V.B);
-    GE_LAUNCH(e->k.reset, grid, GE_RESET_THREADS, e->lds_bytes_inject, stream, Vi, VR, seeds, run, inj, nseed, -1);
-  } else GE_LAUNCH(e->k.reset, grid, GE_RESET_THREADS, e->lds_bytes, stream, V, VR, seeds, run, inj, nseed, -1);
-  if (rc == GE_OK) rc = check_launch("reset kernel");
+  const GePlan &L = e->plan;
+  int nseed = queue ? L.nseed : 0;
+  if (small && nseed > 2) nseed = 2;
+  GeParams V2 = V;  // the view with the launch's own carve: the plan's values, nothing is derived here
+  if (run.inject) { V2.nocolw = 0; V2.nowsort = 0; }  // the injected rows come in the caller's order: this launch keeps the {neighbour, code} list
+  for (int b = 0; b < L.n_buckets && rc == GE_OK; b++) {  // one launch per LDS bucket
+    const GeBucket &K = L.bk[b];
+    if (!K.used) continue;
+    int g = spread(K.graph.grid, V.B, queue), lds = K.graph.lds;
+    if (small && g > 128) g = 128;
+    V2.lds.pre = K.graph.pre;
+    if (run.inject) { V2.lds = L.inject; lds = L.inject.total; }
+    GE_LAUNCH(e->k.reset, g + nseed, GE_RESET_THREADS, lds, stream, V2, VR, seeds, run, inj, nseed, e->n_classes > 0 ? b : -1);
+    rc = check_launch("reset kernel");
+    nseed = 0;  // the seeding workgroups ride in the first launch
+  }
   if (rc != GE_OK) return rc;
   bool baseline = eval_slot_bytes(V) != 0;
   for (const GeParams &C : e->classes) baseline = baseline || eval_slot_bytes(C) != 0;  // (SteinerTree: Kou depends on the class's n_dests)
@@ -836,7 +822,7 @@ extern "C" int ge_reset_pending(ge_engine *e, void *stream) {
     if (e->spares) {  // finished slots with a valid image: one streaming copy each
       int64_t grid = 1024;  // workgroups stride over (slot, part) items; most steps have a few hundred
       if (grid > (int64_t)e->P.B * e->swap_parts) grid = (int64_t)e->P.B * e->swap_parts;
-      GE_LAUNCH(e->k.swap, (int)grid, 256, (step_blocks(e->P.B) + 2) * 4, stream, e->P, e->R, e->RS, e->PS.buf, e->swap_parts);
+      GE_LAUNCH(e->k.swap, (int)grid, 256, prefix_bytes(e->P.B), stream, e->P, e->R, e->RS, e->PS.buf, e->swap_parts);
       rc = check_launch("swap kernel");
       if (rc != GE_OK) return rc;
     }
@@ -969,10 +955,14 @@ extern "C" int ge_timed_empty_burst(ge_engine *e, int32_t k, void *stream, doubl
 extern "C" int ge_debug_occupancy(ge_engine *e, int *out4) {
   if (!e || !out4) return GE_E_BADARG;
   int a = -1, b = -1, c = -1, d = -1;
-  GE_FOR_ENV(e->P.env_type, (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, (ge_k_reset<ENV, false>), GE_RESET_THREADS, e->lds_bytes));
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, ge_k_features64<false>, GE_F64_THREADS, e->feat_lds);
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, ge_k_features<false>, GE_WAVE * e->P.ldsf.waves, e->P.ldsf.total);
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&d, (ge_k_step_path64<true, false>), GE_STEP_BLOCK, e->k.step_lds);
+  const GePlan &L = e->plan;
+  const GeBucket *K = L.bk;  // the engine's first bucket
+  while (!K->used) K++;
+  const void *step = path64(e) ? (const void *)e->k.step_path64[1][e->spares] : (const void *)e->k.step[1];
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, (const void *)e->k.reset, GE_RESET_THREADS, K->graph.lds);
+  if (L.feat_fast) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, (const void *)e->k.features64, GE_F64_THREADS, L.f64_lds);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&c, (const void *)e->k.features, K->gen.threads, K->gen.lds);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&d, step, e->k.step_threads, e->k.step_lds);
   out4[0] = a; out4[1] = b; out4[2] = c; out4[3] = d;
   return GE_OK;
 }
