@@ -738,7 +738,11 @@ template <bool RAGGED>
 GE_GEN_KERNEL ge_k_features(GeParams P, GeRagged R, GeRun run, int pre_off, int bucket) {
   int *pre = (int *)(ge_dyn_smem() + pre_off);
   const bool queue = run.items == GE_ITEMS_QUEUE, list = run.items == GE_ITEMS_LIST;
+  // the fallback launch is normally empty and on every step's critical path: it learns that from one scalar load and leaves, ahead
+  // of the other shards' feature waves; with slots to work on it is a feature kernel like any other
+  if (list) ge_wave_priority(GE_PRIO_PROBE);
   int count = list ? P.buf.work_count[0] : P.B;
+  if (list && count > 0) ge_wave_priority(0);
   if (queue) {
     if (ge_tid() < GE_WAVE) ge_queue_prefix_wave(P, pre, ge_tid());
     ge_sync();

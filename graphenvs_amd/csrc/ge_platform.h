@@ -29,8 +29,16 @@ GE_DEV unsigned char *ge_dyn_smem() {
   return ge_smem_raw;
 }
 GE_DEV void ge_sync() { __syncthreads(); }
-// issue priority of this wave among the waves of its SIMD (s_setprio, 0 = default .. 3)
-GE_DEV void ge_wave_priority(int p) { if (p) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0); }
+// issue priority of this wave among the waves of its SIMD (s_setprio, 0 = default .. 3; the instruction takes an immediate).  The
+// arbitration is between ALL waves resident on the SIMD, whichever kernel and stream they belong to: see GE_PRIO_* below
+GE_DEV void ge_wave_priority(int p) {
+  switch (p) {
+    case 0: __builtin_amdgcn_s_setprio(0); break;
+    case 1: __builtin_amdgcn_s_setprio(1); break;
+    case 2: __builtin_amdgcn_s_setprio(2); break;
+    default: __builtin_amdgcn_s_setprio(3); break;
+  }
+}
 // LDS hand-off between lanes of ONE wave (the other waves of the workgroup do not take part)
 GE_DEV void ge_wave_sync() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); __builtin_amdgcn_wave_barrier(); }
 // Ordering point between the four lanes of a quad that execute identical control flow: LDS operations of one wave
@@ -88,3 +96,13 @@ GE_DEV int ge_clz32(uint32_t v) { return v ? (int)__builtin_clz(v) : 32; }
 #define GE_SET_MAX_DYN_LDS(kernel, bytes) \
   hipFuncSetAttribute((const void *)(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))
 #endif
+
+// Issue priority by role (ge_wave_priority; both builds see these, the CPU harness ignores them).  A shard's step runs at the
+// latency of its own launch chain, beside the other shards' kernels on the same SIMDs: a kernel that is a handful of waves doing
+// dependent round trips outranks the feature kernels, which are the throughput tenants and fill the issue slots the others leave.
+// Only the assignments that were measured beside other engines carry a level: the n <= 64 step kernel and the probe of the generic
+// feature kernel's LIST launch.  ge_k_step, ge_k_step_edge, ge_k_swap and ge_k_feat_combine stay at 0 until the configs that launch
+// them are measured.  The graph kernel stays at 0 (its retrying waves at 1): raised as a whole it gains nothing, and raised above
+// its own seeding workgroups it starves them and the launch ends later (profiles/README.md round 5).
+#define GE_PRIO_STEP 3   // ge_k_step_path64: every wave, from entry to exit
+#define GE_PRIO_PROBE 3  // a LIST-mode launch of ge_k_features until it has read work_count; with work to do it drops to 0

@@ -919,6 +919,7 @@ GE_KERNEL_LB(GE_EDGE_THREADS, 1) ge_k_step_edge(GeParams PG, GeRagged R, const i
 #define GE_ON(bit) (!(GE_ABL & (bit)))  // 1 x flag, 2 bool-mask bytes, 4 gather, 8 policy, 16 state stores, 64 output stores
 template <bool SAMPLE, bool SPARES>
 GE_KERNEL ge_k_step_path64(GeParams P, const int64_t *actions_in, uint64_t policy_seed) {
+  ge_wave_priority(GE_PRIO_STEP);
   const ge_buffers &G = P.buf;
   const int tid = ge_tid();
   const int i0 = ge_bid() * ge_bdim();
