@@ -9,7 +9,8 @@
 """
 from . import utils  # noqa: F401
 from .envs import GraphEnv, make  # noqa: F401
-from .ragged import MixedVectorEnv, RaggedVectorEnv  # noqa: F401
+from .mixed import MixedVectorEnv  # noqa: F401
+from .ragged import RaggedVectorEnv  # noqa: F401
 from .sharded import ShardedVectorEnv  # noqa: F401
 from .vector_env import ENV_IDS, GraphBatch, VectorGraphEnv, make_vec  # noqa: F401
 

@@ -73,6 +73,25 @@ IMAGE_FIELDS = ["x", "edge_index", "edge_attr", "row_ptr", "colw", "scode", "sw6
                 "terminals", "node_bits", "target_bits", "counters", "heuristic", "aux_bits", "mask", "mask_bits", "node_aux",
                 "range_bits", "cover_bits"]
 
+SPARE_QUEUES = ("state", "swap_list", "swap_count", "refill_list", "refill_count")
+QUEUE_BLOCK = 256  # GE_STEP_BLOCK: the step kernels fill the slot queues a segment per this many slots, with one count each
+
+
+def queue_blocks(num_envs):
+    """entries of a queue's count array"""
+    return (num_envs + QUEUE_BLOCK - 1) // QUEUE_BLOCK
+
+
+def buffers(tensors):
+    """ge_buffers over a dict of tensors by field name (None: the engine has no such slab)"""
+    return GeBuffers(**{k: (v.data_ptr() if v is not None else None) for k, v in dict.items(tensors)})
+
+
+def spares(image, queues, period):
+    """ge_spares over a dict of image tensors and the dict of the five queues"""
+    return GeSpares(buffers(image), *(queues[k].data_ptr() for k in SPARE_QUEUES), period)
+
+
 # every symbol include/graphenvs.h declares
 SYMBOLS = [
     "ge_abi_version", "ge_get_layout", "ge_create", "ge_destroy", "ge_ragged_table_bytes", "ge_create_ragged", "ge_reset", "ge_step", "ge_step_only",

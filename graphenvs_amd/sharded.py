@@ -9,7 +9,7 @@ slot g runs seed (seed + g) exactly as in one engine (``env_index_base`` / ``see
 """
 import torch
 
-from .ragged import MixedVectorEnv
+from .mixed import MixedVectorEnv, _member_streams
 from .vector_env import VectorGraphEnv
 
 
@@ -24,7 +24,6 @@ class ShardedVectorEnv(MixedVectorEnv):
             raise ValueError("shards must be between 1 and num_envs")
         stride = int(seed_stride) if seed_stride is not None else num_envs
         if torch.device(device).type == "cuda" and shards > 1 and concurrent:  # no more shards than streams that run beside one another on this device
-            from .ragged import _member_streams
             shards = max(1, min(shards, len(_member_streams(device, shards))))
         sizes = [num_envs // shards + (1 if k < num_envs % shards else 0) for k in range(shards)]
         members, off = [], 0
@@ -54,15 +53,9 @@ class ShardedVectorEnv(MixedVectorEnv):
             for m in self.members[1:]:
                 m.random_rollout(n_steps, policy_seed)
             return self.members[0].timed_rollout(n_steps, policy_seed)
-        cur = torch.cuda.current_stream(self.device)
-        fork = cur.record_event()
-        for st in self._streams:
-            st.wait_event(fork)
-        for m, st in zip(self.members[1:], self._streams[1:]):
-            with torch.cuda.stream(st):
-                m.random_rollout(n_steps, policy_seed)
-        with torch.cuda.stream(self._streams[0]):
-            out = self.members[0].timed_rollout(n_steps, policy_seed)
-        for st in self._streams:
-            cur.wait_stream(st)
-        return out
+        with self._forked():
+            for m, st in zip(self.members[1:], self._streams[1:]):
+                with torch.cuda.stream(st):
+                    m.random_rollout(n_steps, policy_seed)
+            with torch.cuda.stream(self._streams[0]):
+                return self.members[0].timed_rollout(n_steps, policy_seed)

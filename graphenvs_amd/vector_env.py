@@ -154,7 +154,89 @@ class _Slabs(dict):
         raise KeyError(key)
 
 
-class VectorGraphEnv(_VectorBase):
+# the per-slot arrays that are one row per slot whatever the env id and geometry: name -> (trailing shape, dtype).  A uniform engine
+# allocates [B, ...] of each; a multi-class engine keeps ONE of each over all its slots and hands every class its rows.
+PER_SLOT = dict(seed=((), torch.int32), episode=((), torch.int64), mt_state=((_lib.SEED_DEPTH, 2, 624), torch.int32),
+                slot_rec=((2,), torch.int64), heuristic=((), torch.float64), reward=((), torch.float64),
+                terminated=((), torch.uint8), invalid=((), torch.uint8), solved=((), torch.int8),
+                final_cost=((), torch.float64), final_heur=((), torch.float64), final_len=((), torch.int32),
+                counters=((2,), torch.int32))
+
+
+def spare_queues(num_envs, device):
+    """the five queues of the episode prefetch (ge_spares): a state byte and two slot lists per slot, a count per queue block"""
+    z = lambda n, dt: torch.zeros(n, dtype=dt, device=device)
+    nb = _lib.queue_blocks(num_envs)
+    return dict(state=z(num_envs, torch.uint8), swap_list=z(num_envs, torch.int32), swap_count=z(nb, torch.int32),
+                refill_list=z(num_envs, torch.int32), refill_count=z(nb, torch.int32))
+
+
+def slot_seeds(seed, num_envs, env_index_base, device):
+    """the seeds ge_reset / ge_inject_state take, int32 [num_envs] on the device: an integer s gives slot i (global index g =
+    env_index_base + i) the seed (s + g) mod 2^32; a sequence or tensor gives every slot its own"""
+    if isinstance(seed, (int, np.integer)):
+        s = (int(seed) + env_index_base + np.arange(num_envs, dtype=np.int64)) % (1 << 32)
+    else:
+        s = np.asarray(seed.cpu() if torch.is_tensor(seed) else seed, dtype=np.int64).reshape(num_envs)
+        assert ((s >= 0) & (s < (1 << 32))).all(), "seeds must be in [0, 2**32) (np.random.seed requirement)"
+    return torch.from_numpy(s.astype(np.uint32).view(np.int32)).to(device)
+
+
+class EngineHandle:
+    """What owns a ge_* handle: ``_L`` the library, ``_h`` the handle, ``device``, and the calls that are the same for a uniform
+    and a multi-class engine.  A subclass sets those three and ``_actions_scratch`` (int64, one entry per slot)."""
+    _h = None
+    _flat = None
+
+    def _stream(self):
+        if self.device.type == "cuda":
+            return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return C.c_void_p(0)
+
+    def _call(self, name, *args):
+        """ge_<name>(handle, *args), raising with the library's message unless it returns GE_OK"""
+        _lib.check(self._L, getattr(self._L, name)(self._h, *args), name)
+
+    def _quiesce(self):
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+
+    def close(self):
+        if self._h:
+            self._quiesce()
+            self._L.ge_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _vectorized(self, shape):
+        """utils.vectorize_graph of every slot, back to back in one float32 buffer of `shape` (allocated at the first call)"""
+        if self._flat is None:
+            self._flat = torch.empty(shape, dtype=torch.float32, device=self.device)
+        self._call("ge_vectorize", self._flat.data_ptr(), self._stream())
+        return self._flat
+
+    def sample_random_actions(self, policy_seed=0, out=None):
+        out = self._actions_scratch if out is None else out
+        self._call("ge_sample_actions", int(policy_seed), out.data_ptr(), self._stream())
+        return out
+
+    def random_rollout(self, n_steps, policy_seed=0):
+        self._call("ge_random_rollout", int(policy_seed), int(n_steps), self._actions_scratch.data_ptr(), self._stream())
+
+    def timed_rollout(self, n_steps, policy_seed=0):
+        """the rollout with a HIP-event pair around the policy, the step kernel and the autoreset launches of every step (profiling)"""
+        a, b, c = C.c_double(), C.c_double(), C.c_double()
+        self._call("ge_timed_rollout", int(policy_seed), int(n_steps), self._actions_scratch.data_ptr(), self._stream(),
+                   C.byref(a), C.byref(b), C.byref(c))
+        return dict(step_ms=a.value, reset_ms=b.value, policy_ms=c.value)
+
+
+class VectorGraphEnv(EngineHandle, _VectorBase):
     """B independent envs of one id on one GPU.  One instance per process/GPU; no global state.  A subclass of
     gymnasium.vector.VectorEnv when gymnasium is installed (num_envs, single_*_space, *_space, metadata['autoreset_mode'])."""
 
@@ -199,7 +281,7 @@ class VectorGraphEnv(_VectorBase):
         self.T = T
         dev = self.device
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        t = {}
+        t = {k: z((B,) + shape, dt) for k, (shape, dt) in PER_SLOT.items()}
         t["x"] = z((B * n, self.F), torch.float32)
         t["edge_index"] = z((2, B * E), torch.int64)
         t["edge_attr"] = z((B * E, self.Fe), torch.float32)
@@ -210,27 +292,14 @@ class VectorGraphEnv(_VectorBase):
         t["adj_bits"] = z((B * n, W), torch.int64)
         t["node_rec"] = z((B * n, 2), torch.int64) if W == 1 else None
         t["rev_edge"] = z((B * E,), torch.int32) if edge_env else None
-        t["slot_rec"] = z((B, 2), torch.int64)
         t["terminals"] = z((B, T), torch.int32)
         t["node_bits"] = z((B, W), torch.int64)
         t["target_bits"] = z((B, W), torch.int64)
-        t["counters"] = z((B, 2), torch.int32)
-        t["seed"] = z((B,), torch.int32)
-        t["episode"] = z((B,), torch.int64)
-        t["heuristic"] = z((B,), torch.float64)
-        t["mt_state"] = z((B, _lib.SEED_DEPTH, 2, 624), torch.int32)
         t["aux_bits"] = z((B,), torch.int64) if (env_id == "DistributionCenter-v0" and W == 1) else None
         t["mask"] = z((B, A), torch.uint8)
         t["mask_bits"] = z((B, AW), torch.int64)
-        t["reward"] = z((B,), torch.float64)
-        t["terminated"] = z((B,), torch.uint8)
-        t["invalid"] = z((B,), torch.uint8)
-        t["solved"] = z((B,), torch.int8)
-        t["final_cost"] = z((B,), torch.float64)
-        t["final_heur"] = z((B,), torch.float64)
-        t["final_len"] = z((B,), torch.int32)
         t["reset_list"] = z((B,), torch.int32)
-        t["reset_count"] = z(((B + 255) // 256,), torch.int32)
+        t["reset_count"] = z((_lib.queue_blocks(B),), torch.int32)
         t["work_list"] = z((B,), torch.int32)
         t["work_count"] = z((4,), torch.int32)
         t["feat_scratch"] = z((B, lay.feat_parts, n), torch.float64) if lay.feat_parts > 1 else None
@@ -251,8 +320,8 @@ class VectorGraphEnv(_VectorBase):
                 assert v.dtype == t[k].dtype and v.numel() >= (t[k].numel() if k != "edge_index" else 0), k
                 t[k] = v
         self.node_id_base = int(node_id_base)
-        self.t = t = _Slabs(t)
-        self.bufs = _lib.GeBuffers(**{k: (v.data_ptr() if v is not None else None) for k, v in dict.items(t)})
+        self.t = t = _Slabs((k, t[k]) for k in _lib.BUFFER_FIELDS)  # (in ge_buffers' order; a field without a line above is a KeyError)
+        self.bufs = _lib.buffers(t)
         h = C.c_void_p()
         if not _defer_create:  # (a size class of a multi-class engine is created by RaggedVectorEnv, all classes at once)
             _lib.check(self._L, self._L.ge_create(C.byref(self.cfg), C.byref(self.bufs), C.byref(h)), "ge_create")
@@ -274,7 +343,6 @@ class VectorGraphEnv(_VectorBase):
         self._ptr = torch.arange(B + 1, device=dev, dtype=torch.int64) * n + int(node_id_base)
         self._truncated = torch.zeros(B, dtype=torch.bool, device=dev)
         self._actions_scratch = z((B,), torch.int64)
-        self._flat = None
         self._was_reset = False
         self._streams = False  # stream_state holds the streams of a reset (continue_streams)
         self.single_action_space = _Space(n=(self.m if edge_env else n), mask_size=A)  # steiner_tree.py:43, multicast_routing.py:67
@@ -318,34 +386,9 @@ class VectorGraphEnv(_VectorBase):
         return img
 
     def _attach_spares(self):
-        B, dev = self.num_envs, self.device
-        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
-        img = self._image_tensors()
-        sp = dict(state=z((B,), torch.uint8), swap_list=z((B,), torch.int32), swap_count=z(((B + 255) // 256,), torch.int32),
-                  refill_list=z((B,), torch.int32), refill_count=z(((B + 255) // 256,), torch.int32))
+        img, sp = self._image_tensors(), spare_queues(self.num_envs, self.device)
         self.spare = dict(image=img, **sp)
-        rec = _lib.GeSpares(_lib.GeBuffers(**{k: (v.data_ptr() if v is not None else None) for k, v in img.items()}),
-                            *(sp[k].data_ptr() for k in ("state", "swap_list", "swap_count", "refill_list", "refill_count")), self.prefetch)
-        _lib.check(self._L, self._L.ge_attach_spares(self._h, C.byref(rec), None), "ge_attach_spares")
-
-    # ------------------------------------------------------------------ plumbing
-    def _stream(self):
-        if self.device.type == "cuda":
-            return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-        return C.c_void_p(0)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h:
-            if self.device.type == "cuda":
-                torch.cuda.synchronize(self.device)
-            self._L.ge_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._call("ge_attach_spares", C.byref(_lib.spares(img, sp, self.prefetch)), None)
 
     # ------------------------------------------------------------------ views
     def graph(self):
@@ -355,10 +398,7 @@ class VectorGraphEnv(_VectorBase):
 
     def flat_obs(self):
         """utils.vectorize_graph of every slot: float32 [B, obs_len] (utils.py:87-88)."""
-        if self._flat is None:
-            self._flat = torch.empty((self.num_envs, self.obs_len), dtype=torch.float32, device=self.device)
-        _lib.check(self._L, self._L.ge_vectorize(self._h, self._flat.data_ptr(), self._stream()), "ge_vectorize")
-        return self._flat
+        return self._vectorized((self.num_envs, self.obs_len))
 
     def _obs(self):
         return self.flat_obs() if self.obs_mode == "flat" else self.graph()
@@ -398,32 +438,23 @@ class VectorGraphEnv(_VectorBase):
 
     # ------------------------------------------------------------------ gym surface
     def _seed_tensor(self, seed):
-        B = self.num_envs
         if seed is None:
             if not self._was_reset:
                 seed = 0
             else:  # next episode of every slot
-                s = (self.t["seed"].cpu().numpy().view(np.uint32).astype(np.int64) + self.seed_stride) % (1 << 32)
-                return torch.from_numpy(s.astype(np.uint32).view(np.int32)).to(self.device)
-        if isinstance(seed, (int, np.integer)):
-            s = (int(seed) + self.env_index_base + np.arange(B, dtype=np.int64)) % (1 << 32)
-        else:
-            s = np.asarray(seed.cpu() if torch.is_tensor(seed) else seed, dtype=np.int64).reshape(B)
-            assert ((s >= 0) & (s < (1 << 32))).all(), "seeds must be in [0, 2**32) (np.random.seed requirement)"
-        return torch.from_numpy(s.astype(np.uint32).view(np.int32)).to(self.device)
+                seed = (self.t["seed"].cpu().numpy().view(np.uint32).astype(np.int64) + self.seed_stride) % (1 << 32)
+        return slot_seeds(seed, self.num_envs, self.env_index_base, self.device)
 
     def reset(self, seed=None, options=None):
         """reset(seed=s): slot i (global index g) runs the reference's reset(seed=(s+g) mod 2^32); a
         sequence/tensor gives every slot its own seed.  reset() without a seed: see ``continue_streams``."""
         if seed is None and self._streams:
-            _lib.check(self._L, self._L.ge_reset_continue(self._h, self._stream()), "ge_reset_continue")
-            out = (self._obs(), self._info(False))
-            return self._copied(out) if self.copy_outputs else out
-        seeds = self._seed_tensor(seed)
-        self._seeds_keepalive = seeds
-        _lib.check(self._L, self._L.ge_reset(self._h, seeds.data_ptr(), self._stream()), "ge_reset")
-        self._was_reset = True
-        self._streams = self.continue_streams
+            self._call("ge_reset_continue", self._stream())
+        else:
+            self._seeds_keepalive = seeds = self._seed_tensor(seed)
+            self._call("ge_reset", seeds.data_ptr(), self._stream())
+            self._was_reset = True
+            self._streams = self.continue_streams
         out = (self._obs(), self._info(False))
         return self._copied(out) if self.copy_outputs else out
 
@@ -437,7 +468,7 @@ class VectorGraphEnv(_VectorBase):
         assert actions.shape == (self.num_envs,)
         assert self._was_reset, "call reset() (or inject_state()) before step()"
         self._act_keepalive = actions
-        _lib.check(self._L, self._L.ge_step(self._h, actions.data_ptr(), self._stream()), "ge_step")
+        self._call("ge_step", actions.data_ptr(), self._stream())
         t = self.t
         if self.strict and bool(t["invalid"].any()):
             bad = torch.nonzero(t["invalid"]).flatten().tolist()
@@ -446,46 +477,24 @@ class VectorGraphEnv(_VectorBase):
         return self._copied(out) if self.copy_outputs else out
 
     # ------------------------------------------------------------------ extras
-    def sample_random_actions(self, policy_seed=0, out=None):
-        out = self._actions_scratch if out is None else out
-        _lib.check(self._L, self._L.ge_sample_actions(self._h, int(policy_seed), out.data_ptr(), self._stream()),
-                   "ge_sample_actions")
-        return out
-
-    def random_rollout(self, n_steps, policy_seed=0):
-        _lib.check(self._L, self._L.ge_random_rollout(self._h, int(policy_seed), int(n_steps),
-                                                      self._actions_scratch.data_ptr(), self._stream()),
-                   "ge_random_rollout")
-
-    def timed_rollout(self, n_steps, policy_seed=0):
-        a, b, c = C.c_double(), C.c_double(), C.c_double()
-        _lib.check(self._L, self._L.ge_timed_rollout(self._h, int(policy_seed), int(n_steps),
-                                                     self._actions_scratch.data_ptr(), self._stream(),
-                                                     C.byref(a), C.byref(b), C.byref(c)), "ge_timed_rollout")
-        return dict(step_ms=a.value, reset_ms=b.value, policy_ms=c.value)
-
     def timed_step_burst_raw_ms(self, k, policy_seed=0):
         """elapsed ms between one pair of HIP events around k back-to-back (sample+)step launches (k = 0: the bare
         event pair, i.e. the measurement overhead)."""
         ms = C.c_double()
-        _lib.check(self._L, self._L.ge_timed_step_burst(self._h, int(policy_seed), int(k), self._actions_scratch.data_ptr(),
-                                                        self._stream(), C.byref(ms)), "ge_timed_step_burst")
+        self._call("ge_timed_step_burst", int(policy_seed), int(k), self._actions_scratch.data_ptr(), self._stream(), C.byref(ms))
         return ms.value
 
     def timed_step_burst(self, k, policy_seed=0):
         """k back-to-back (sample+)step launches between one pair of HIP events, no autoreset in between; returns
         the average launch duration in microseconds."""
-        ms = C.c_double()
-        _lib.check(self._L, self._L.ge_timed_step_burst(self._h, int(policy_seed), int(k), self._actions_scratch.data_ptr(),
-                                                        self._stream(), C.byref(ms)), "ge_timed_step_burst")
-        return ms.value * 1e3 / k
+        return self.timed_step_burst_raw_ms(k, policy_seed) * 1e3 / k
 
     def launch_floor_us(self, k=5, reps=9):
         """what an EMPTY launch of the step kernel's shape takes (median of `reps` bursts of k), microseconds"""
         ms, vals = C.c_double(), []
         empty = sorted(self.timed_step_burst_raw_ms(0) for _ in range(reps))[reps // 2]
         for _ in range(reps):
-            _lib.check(self._L, self._L.ge_timed_empty_burst(self._h, int(k), self._stream(), C.byref(ms)), "ge_timed_empty_burst")
+            self._call("ge_timed_empty_burst", int(k), self._stream(), C.byref(ms))
             vals.append((ms.value - empty) * 1e3 / k)
         return sorted(vals)[reps // 2]
 
@@ -516,22 +525,12 @@ class VectorGraphEnv(_VectorBase):
             assert term.shape == (self.num_envs, self.T)
         assert links.shape == (self.num_envs, self.E, 2) and wcode.shape == (self.num_envs, self.E)
         assert x.shape == (self.num_envs, self.n, self.F)
-        sd = None
-        if seeds is not None:
-            sn = np.asarray(seeds.cpu() if torch.is_tensor(seeds) else seeds, dtype=np.int64).reshape(self.num_envs)
-            assert ((sn >= 0) & (sn < (1 << 32))).all(), "seeds must be in [0, 2**32)"
-            sd = torch.from_numpy(sn.astype(np.uint32).view(np.int32)).to(dev)
+        sd = None if seeds is None else slot_seeds(seeds, self.num_envs, 0, dev)
         self._inj_keepalive = (links, wcode, x, term, sd)
-        _lib.check(self._L, self._L.ge_inject_state(self._h, links.data_ptr(), wcode.data_ptr(), x.data_ptr(),
-                                                    term.data_ptr() if term is not None else None,
-                                                    sd.data_ptr() if sd is not None else None, self._stream()),
-                   "ge_inject_state")
+        self._call("ge_inject_state", links.data_ptr(), wcode.data_ptr(), x.data_ptr(), term.data_ptr() if term is not None else None,
+                   sd.data_ptr() if sd is not None else None, self._stream())
         self._was_reset = True
         return self._obs(), self._info(False)
-
-    def _quiesce(self):
-        if self.device.type == "cuda":
-            torch.cuda.synchronize(self.device)
 
     def state_dict(self):
         """Snapshot of every engine slab: the whole state of the batch, generator states included."""
@@ -554,19 +553,19 @@ class VectorGraphEnv(_VectorBase):
             # next-step autoreset: a slot that finished in the snapshot's last step waits for its regeneration (status 2), queued
             # either for the regeneration in place (reset_list, part of the snapshot) or -- it had a valid image -- for the swap
             # (swap_list, which is not: the images are gone).  Every such slot goes through the regeneration queue, in the layout the
-            # step kernels write (a segment per 256 slots, slot order), and this engine's own swap queue is emptied.
+            # step kernels write (a segment per QUEUE_BLOCK slots, slot order), and this engine's own swap queue is emptied.
             self.spare["swap_count"].zero_()
-            B = self.num_envs
+            B, QB = self.num_envs, _lib.QUEUE_BLOCK
             fin = (self.t["status"] == 2).to(torch.int32)
-            pad = torch.zeros(((B + 255) // 256) * 256, dtype=torch.int32, device=self.device)
+            pad = torch.zeros(_lib.queue_blocks(B) * QB, dtype=torch.int32, device=self.device)
             pad[:B] = fin
-            blocks = pad.view(-1, 256)
+            blocks = pad.view(-1, QB)
             rank = torch.cumsum(blocks, dim=1) - blocks
-            slot = torch.arange(pad.numel(), device=self.device, dtype=torch.int32).view(-1, 256)
-            pos = (slot - slot % 256 + rank)[blocks.bool()].to(torch.int64)
+            slot = torch.arange(pad.numel(), device=self.device, dtype=torch.int32).view(-1, QB)
+            pos = (slot - slot % QB + rank)[blocks.bool()].to(torch.int64)
             dict.__getitem__(self.t, "reset_list")[pos] = slot[blocks.bool()]
             dict.__getitem__(self.t, "reset_count").copy_(blocks.sum(dim=1).to(torch.int32))
-        _lib.check(self._L, self._L.ge_mark_restored(self._h), "ge_mark_restored")
+        self._call("ge_mark_restored")
         self._was_reset = True
         self._streams = self.continue_streams and "stream_state" in sd
         self._quiesce()

@@ -266,3 +266,25 @@ def check_timed_rollout_equals_random_rollout(ge, device, lib, env_id, kw, B=300
     assert int(a.t["episode"].sum()) > 0 and int(a.t["tstep"].sum()) > 0
     a.check_device_errors(); b.check_device_errors()
     a.close(); b.close()
+
+
+def check_sharded_timed_rollout_equals_random_rollout(ge, device="cuda"):
+    """ShardedVectorEnv.timed_rollout -- shard 0 timed, the other shards rolling out beside it between one fork and one join -- leaves
+    what random_rollout leaves.  Ten slots of ten nodes: the smallest batch that still gives three uneven shards (4 / 3 / 3) and
+    several finished episodes in 25 steps."""
+    make = lambda: ge.make_vec("ShortestPath-v0", 10, shards=3, prefetch=0, n_nodes=10, n_edges=20, device=device)
+    many, twin = make(), make()
+    assert many.shards == twin.shards == len(many.members)  # (the stream probe may grant fewer than three)
+    many.reset(seed=7); twin.reset(seed=7)
+    ms = many.timed_rollout(25, 5)
+    twin.random_rollout(25, 5)
+    for m in many.members + twin.members:
+        m._quiesce()
+    assert set(ms) == {"step_ms", "reset_ms", "policy_ms"}
+    for key in ("episode", "tstep", "seed", "reward", "terminated", "cost", "solved"):
+        assert torch.equal(many.gather(key), twin.gather(key)), key
+    for key in ("x", "mask"):
+        assert torch.equal(torch.cat([m.t[key] for m in many.members]), torch.cat([m.t[key] for m in twin.members])), key
+    assert int(many.gather("episode").sum()) > 0  # autoreset really ran
+    many.check_device_errors(); twin.check_device_errors()
+    many.close(); twin.close()

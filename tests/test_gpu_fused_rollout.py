@@ -103,3 +103,7 @@ def test_fused_rollout_of_the_multi_class_engine_matches_oracle_and_unfused_twin
                                        ("SteinerTree-v0", dict(n_nodes=40, n_edges=100))])
 def test_timed_rollout_leaves_what_random_rollout_leaves(env_id, kw):
     fc.check_timed_rollout_equals_random_rollout(_ge(), "cuda", None, env_id, kw)
+
+
+def test_sharded_timed_rollout_leaves_what_random_rollout_leaves():
+    fc.check_sharded_timed_rollout_equals_random_rollout(_ge())
