@@ -115,6 +115,16 @@ GE_DEV int ge_nth_set_bit(uint64_t word, uint32_t r) {
   return ge_ctz64(word);
 }
 
+// no action (-1): the mask has no set bit (cnt == 0), or the slot is frozen (status 1 / 4)
+GE_DEV bool ge_policy_idle(uint32_t cnt, int status) { return !cnt || status == 1 || status == 4; }
+
+// the draw of global slot gi at its step ts: which of the cnt set bits of the mask row is taken, counted from bit 0
+// (oracle.policy_pick).  How the r-th set bit is found is the caller's: a row in registers, a looped row, a row dealt over a quad.
+GE_DEV uint32_t ge_policy_draw(uint64_t policy_seed, uint64_t gi, uint64_t ts, uint32_t cnt) {
+  const uint64_t z = ge_mix64(policy_seed + gi * 0x9E3779B97F4A7C15ull + ts * 0xD1B54A32D192ED03ull);
+  return (uint32_t)(((z >> 32) * (uint64_t)cnt) >> 32);
+}
+
 // the action of slot i under that policy (-1: empty mask, or a frozen slot)
 // up to eight words of a slot's row in one round trip: every load unconditional (a word past the end re-reads word 0) and the
 // words that do not exist zeroed afterwards.  A `for (w < W)` over global memory with a run-time bound is one load, one wait per
@@ -134,10 +144,8 @@ GE_DEV int64_t ge_policy_pick(const GeParams &P, int i, uint64_t policy_seed) {
     uint32_t cnt = 0;
 #pragma unroll
     for (int w = 0; w < 8; w++) cnt += (uint32_t)ge_popc64(m[w]);
-    if (!cnt || ge_rec_status(packed) == 1 || ge_rec_status(packed) == 4) return -1;
-    const uint64_t gi = (uint64_t)(P.env_index_base + i), ts = ge_rec_tstep(packed);
-    const uint64_t z = ge_mix64(policy_seed + gi * 0x9E3779B97F4A7C15ull + ts * 0xD1B54A32D192ED03ull);
-    uint32_t r = (uint32_t)(((z >> 32) * (uint64_t)cnt) >> 32);
+    if (ge_policy_idle(cnt, ge_rec_status(packed))) return -1;
+    uint32_t r = ge_policy_draw(policy_seed, (uint64_t)(P.env_index_base + i), ge_rec_tstep(packed), cnt);
     int64_t pick = -1;
 #pragma unroll
     for (int w = 0; w < 8; w++) {
@@ -149,16 +157,82 @@ GE_DEV int64_t ge_policy_pick(const GeParams &P, int i, uint64_t policy_seed) {
   }
   uint32_t cnt = 0;
   for (int w = 0; w < P.AW; w++) cnt += (uint32_t)ge_popc64(mb[w]);
-  if (!cnt || ge_rec_status(packed) == 1 || ge_rec_status(packed) == 4) return -1;
-  uint64_t gi = (uint64_t)(P.env_index_base + i), ts = ge_rec_tstep(packed);
-  uint64_t z = ge_mix64(policy_seed + gi * 0x9E3779B97F4A7C15ull + ts * 0xD1B54A32D192ED03ull);
-  uint32_t r = (uint32_t)(((z >> 32) * (uint64_t)cnt) >> 32);
+  if (ge_policy_idle(cnt, ge_rec_status(packed))) return -1;
+  uint32_t r = ge_policy_draw(policy_seed, (uint64_t)(P.env_index_base + i), ge_rec_tstep(packed), cnt);
   for (int w = 0; w < P.AW; w++) {
     uint64_t word = mb[w]; uint32_t pc = (uint32_t)ge_popc64(word);
     if (r < pc) return (int64_t)w * 64 + ge_nth_set_bit(word, r);
     r -= pc;
   }
   return -1;
+}
+
+// the low eight bits of b8 as eight bool bytes, bit k -> byte k: the multiply spreads the byte, the mask picks bit k of copy k, the
+// add-and-shift turns "non-zero" into 1
+GE_DEV uint64_t ge_bits8_to_bytes(uint64_t b8) {
+  const uint64_t y = ((b8 & 0xffull) * 0x0101010101010101ull) & 0x8040201008040201ull;
+  return ((y + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;
+}
+
+// The workgroup's part of the bool mask slab: out = the [nb, A] bytes of its nb slots (contiguous), stage = their new mask rows in
+// LDS, `stride` words apart; a slot whose flag is 0 keeps the bytes it has.  Eight bytes per store where a row is whole groups.
+// (stride 1, the n <= 64 kernel: a one-word row has no word index to compute.)
+GE_DEV void ge_mask_slab_tail(uint8_t *out, const uint64_t *stage, int stride, const uint8_t *flag, int nb, int A, int tid) {
+  if ((A & 7) == 0) {
+    const int groups = nb * (A >> 3);
+    for (int g = tid; g < groups; g += ge_bdim()) {
+      const int e = (g << 3) / A, v0 = (g << 3) % A;
+      if (!flag[e]) continue;
+      *(uint64_t *)(out + ((int64_t)g << 3)) = ge_bits8_to_bytes(stage[e * stride + (stride == 1 ? 0 : v0 >> 6)] >> (v0 & 63));
+    }
+  } else {
+    const int total = nb * A;
+    for (int idx = tid; idx < total; idx += ge_bdim()) {
+      const int e = idx / A, v = idx % A;
+      if (!flag[e]) continue;
+      out[idx] = (uint8_t)((stage[e * stride + (stride == 1 ? 0 : v >> 6)] >> (v & 63)) & 1ull);
+    }
+  }
+}
+
+// End of a slot's transition, by the thread that owns the slot (i: the slot inside its class, buffers of P; ig: the global slot,
+// spare_state of the engine-wide PG; rec: the slot record as loaded before the move): the four outputs, the step count, the
+// episode length, and for an episode that ends here final_* and the reset / swap request.  len_slot: the counter that holds the
+// length -- 1: counted here, one per move; 0: the env's transition has counted it already (TSP, DensestSubgraph).
+// Returns whether the reset kernel rewrites the whole slot right away (same-step autoreset): its new mask need not be written.
+GE_DEV bool ge_end_transition(const GeParams &PG, const GeParams &P, int ig, int i, ulonglong2 rec, bool acted, double reward, int done,
+                              int invalid, int solved, double cost, double final_cost, int len_slot, int head_out,
+                              bool &want_reset, bool &want_swap) {
+  const ge_buffers &G = P.buf;
+  const int st = ge_rec_status(rec.y);
+  bool rewritten = false;
+  G.reward[i] = reward;
+  G.terminated[i] = (uint8_t)done;
+  G.invalid[i] = (uint8_t)invalid;
+  G.solved[i] = (int8_t)solved;
+  int st_out = (st == 3) ? 0 : st;  // a slot regenerated at the start of this step (next-step autoreset) runs from the next step on
+  uint64_t ts = ge_rec_tstep(rec.y);
+  if (acted) {
+    int len = G.counters[i * 2 + len_slot];
+    if (len_slot) { len += 1; G.counters[i * 2 + 1] = len; }
+    ts = (ts + 1) & 0xffffffffull;
+    if (done) {
+      G.final_cost[i] = final_cost;
+      G.final_len[i] = len;
+      if (P.autoreset != 1) G.final_heur[i] = G.heuristic[i];  // same-step autoreset: the reset kernel copies it before it overwrites `heuristic`
+      if (P.autoreset) {
+        want_reset = true;
+        want_swap = PG.spare_state && PG.spare_state[ig];  // the slot's next episode waits in its spare image
+        if (want_swap) PG.spare_state[ig] = 0;
+        st_out = 2;
+        rewritten = P.autoreset == 1;
+      } else {
+        st_out = 1;
+      }
+    }
+  }
+  if (acted || st == 3) ((ulonglong2 *)G.slot_rec)[i] = make_ulonglong2(ge_f64_as_u64(cost), ge_rec_make(head_out, st_out, ge_rec_aux(rec.y), ts));
+  return rewritten;
 }
 
 // SAMPLE: the device policy is evaluated here (one launch per rollout step) and the action is also written to actions_out.
@@ -575,38 +649,13 @@ GE_KERNEL ge_k_step(GeParams PG, GeRagged R, const int64_t *actions, uint64_t po
         }
       }
     }
-    G.reward[i] = reward;
-    G.terminated[i] = (uint8_t)done;
-    G.invalid[i] = (uint8_t)invalid;
-    G.solved[i] = (int8_t)solved;
-    int st_out = (st == 3) ? 0 : st;  // a slot regenerated at the start of this step (next-step autoreset) runs from the next step on
-    uint64_t ts = ge_rec_tstep(rec.y);
-    if (acted) {
-      int len = G.counters[i * 2 + (t == GE_DENSEST_SUBGRAPH || t == GE_TSP ? 0 : 1)];
-      if (!(t == GE_DENSEST_SUBGRAPH || t == GE_TSP)) { len += 1; G.counters[i * 2 + 1] = len; }
-      ts = (ts + 1) & 0xffffffffull;
-      if (done) {
-        G.final_cost[i] = cost_hidden ? -1.0 : (cost_lagged ? cost_before : cost);
-        G.final_len[i] = len;
-        if (P.autoreset != 1) G.final_heur[i] = G.heuristic[i];  // same-step autoreset: the reset kernel copies it before it overwrites `heuristic`
-        if (P.autoreset) {
-          want_reset = true;
-          want_swap = PG.spare_state && PG.spare_state[ig];  // the slot's next episode waits in its spare image
-          if (want_swap) PG.spare_state[ig] = 0;
-          st_out = 2;
-          if (P.autoreset == 1) wrote_mask = false;  // same-step: the reset kernel rewrites the whole slot right away
-        } else {
-          st_out = 1;
-        }
-      }
-    }
-    if (acted || st == 3) ((ulonglong2 *)G.slot_rec)[i] = make_ulonglong2(ge_f64_as_u64(cost), ge_rec_make(head_out, st_out, ge_rec_aux(rec.y), ts));
+    if (ge_end_transition(PG, P, ig, i, rec, acted, reward, done, invalid, solved, cost, cost_hidden ? -1.0 : (cost_lagged ? cost_before : cost),
+                          (t == GE_DENSEST_SUBGRAPH || t == GE_TSP) ? 0 : 1, head_out, want_reset, want_swap)) wrote_mask = false;
     if (wrote_mask && !edge_mask) for (int w = 0; w < W; w++) G.mask_bits[(int64_t)i * AW + w] = stage[tid * WS + w];
     if constexpr (RAGGED) {  // the slot's own thread expands its mask words to bool bytes
       if (wrote_mask && !edge_mask) {
         uint8_t *out = G.mask + (int64_t)i * A;
-        // eight bool bytes per store where the row's bytes are 8-aligned (bit k of a byte of the set -> byte k: the multiply spreads
-        // the byte, the mask picks bit k of copy k, the add-and-shift turns "non-zero" into 1), single bytes at the ragged ends
+        // eight bool bytes per store where the row's bytes are 8-aligned (ge_bits8_to_bytes), single bytes at the ragged ends
         int v = 0;
         const int head_bytes = (int)((8 - ((uintptr_t)out & 7)) & 7);
         for (; v < A && v < head_bytes; v++) out[v] = (uint8_t)((stage[tid * WS + (v >> 6)] >> (v & 63)) & 1ull);
@@ -614,10 +663,7 @@ GE_KERNEL ge_k_step(GeParams PG, GeRagged R, const int64_t *actions, uint64_t po
           const int w = v >> 6, sh = v & 63;
           uint64_t b8 = stage[tid * WS + w] >> sh;
           if (sh > 56 && w + 1 < (A + 63) / 64) b8 |= stage[tid * WS + w + 1] << (64 - sh);
-          b8 &= 0xffull;
-          uint64_t y = (b8 * 0x0101010101010101ull) & 0x8040201008040201ull;
-          y = ((y + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;
-          *(uint64_t *)(out + v) = y;
+          *(uint64_t *)(out + v) = ge_bits8_to_bytes(b8);
         }
         for (; v < A; v++) out[v] = (uint8_t)((stage[tid * WS + (v >> 6)] >> (v & 63)) & 1ull);
       }
@@ -631,25 +677,7 @@ GE_KERNEL ge_k_step(GeParams PG, GeRagged R, const int64_t *actions, uint64_t po
   // ---- bool mask slab: [B, n] bytes, this workgroup owns the contiguous range of its slots
   int nb = P.B - i0; if (nb > ge_bdim()) nb = ge_bdim();
   if (nb <= 0) return;
-  uint8_t *out = G.mask + (int64_t)i0 * A;
-  if ((A & 7) == 0) {
-    int groups = nb * (A >> 3);
-    for (int g = tid; g < groups; g += ge_bdim()) {
-      int e = (g << 3) / A, v0 = (g << 3) % A;
-      if (!flag[e]) continue;
-      uint64_t b8 = (stage[e * W + (v0 >> 6)] >> (v0 & 63)) & 0xffull;
-      uint64_t y = (b8 * 0x0101010101010101ull) & 0x8040201008040201ull;
-      y = ((y + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;
-      *(uint64_t *)(out + ((int64_t)g << 3)) = y;
-    }
-  } else {
-    int total = nb * A;
-    for (int idx = tid; idx < total; idx += ge_bdim()) {
-      int e = idx / A, v = idx % A;
-      if (!flag[e]) continue;
-      out[idx] = (uint8_t)((stage[e * W + (v >> 6)] >> (v & 63)) & 1ull);
-    }
-  }
+  ge_mask_slab_tail(G.mask + (int64_t)i0 * A, stage, W, flag, nb, A, tid);
 }
 
 // Edge-action envs (SteinerTree, MulticastRouting: one action per directed edge, [B, 2m] masks), a QUAD of lanes per slot.
@@ -731,7 +759,7 @@ GE_KERNEL_LB(GE_EDGE_THREADS, 1) ge_k_step_edge(GeParams PG, GeRagged R, const i
     const ulonglong2 rec = ((const ulonglong2 *)G.slot_rec)[i];
     ge_quad_sync();  // the four lanes have read the record before lane 0 may rewrite it (lockstep on the GPU; the CPU harness runs lanes one after another)
     const int st = ge_rec_status(rec.y);
-    uint64_t ts = ge_rec_tstep(rec.y);
+    const uint64_t ts = ge_rec_tstep(rec.y);
     // ---- action
     int64_t a64;
     if (SAMPLE) {
@@ -745,9 +773,8 @@ GE_KERNEL_LB(GE_EDGE_THREADS, 1) ge_k_step_edge(GeParams PG, GeRagged R, const i
         cnt += ctot[j];
       }
       a64 = -1;
-      if (cnt && st != 1 && st != 4) {
-        const uint64_t z = ge_mix64(policy_seed + (uint64_t)(P.env_index_base + i) * 0x9E3779B97F4A7C15ull + ts * 0xD1B54A32D192ED03ull);
-        uint32_t r = (uint32_t)(((z >> 32) * (uint64_t)cnt) >> 32);
+      if (!ge_policy_idle(cnt, st)) {
+        uint32_t r = ge_policy_draw(policy_seed, (uint64_t)(P.env_index_base + i), ts, cnt);
         int jsel = 0;
 #pragma unroll
         for (int j = 0; j < 7; j++) if (jsel == j && r >= ctot[j]) { r -= ctot[j]; jsel = j + 1; }
@@ -876,30 +903,8 @@ GE_KERNEL_LB(GE_EDGE_THREADS, 1) ge_k_step_edge(GeParams PG, GeRagged R, const i
         }
       }
     }
-    if (q == 0) {
-      G.reward[i] = reward;
-      G.terminated[i] = (uint8_t)done;
-      G.invalid[i] = (uint8_t)invalid;
-      G.solved[i] = (int8_t)solved;
-      int st_out = (st == 3) ? 0 : st;  // a slot regenerated at the start of this step (next-step autoreset) runs from the next step on
-      if (acted) {
-        const int len = G.counters[i * 2 + 1] + 1;
-        G.counters[i * 2 + 1] = len;
-        ts = (ts + 1) & 0xffffffffull;
-        if (done) {
-          G.final_cost[i] = cost_hidden ? -1.0 : cost;
-          G.final_len[i] = len;
-          if (P.autoreset != 1) G.final_heur[i] = G.heuristic[i];
-          if (P.autoreset) {
-            want_reset = true;
-            want_swap = PG.spare_state && PG.spare_state[ig];
-            if (want_swap) PG.spare_state[ig] = 0;
-            st_out = 2;
-          } else st_out = 1;
-        }
-      }
-      if (acted || st == 3) ((ulonglong2 *)G.slot_rec)[i] = make_ulonglong2(ge_f64_as_u64(cost), ge_rec_make(ge_rec_head(rec.y), st_out, ge_rec_aux(rec.y), ts));
-    }
+    if (q == 0)  // (the mask row is updated in place above: nothing to skip after a same-step reset request)
+      ge_end_transition(PG, P, ig, i, rec, acted, reward, done, invalid, solved, cost, cost_hidden ? -1.0 : cost, 1, ge_rec_head(rec.y), want_reset, want_swap);
   }
   ge_enqueue_reset(PG, wcnt, i0, ig, tid, want_reset, want_swap);  // contains the barrier; global slot ids; only lane 0 of a quad ever wants
 }
@@ -913,10 +918,6 @@ GE_KERNEL_LB(GE_EDGE_THREADS, 1) ge_k_step_edge(GeParams PG, GeRagged R, const i
 // from a's record (rank of the head among a's neighbours): the head's own record is never needed, and nothing about the
 // head is carried in the slot state beyond its index.  Optional fused sampling of the random policy (SAMPLE) so a rollout
 // step is a single launch.
-#ifndef GE_ABL
-#define GE_ABL 0  // diagnostic ablation bits (tools/step_variants.py, results are wrong by construction); 0 when shipped
-#endif
-#define GE_ON(bit) (!(GE_ABL & (bit)))  // 1 x flag, 2 bool-mask bytes, 4 gather, 8 policy, 16 state stores, 64 output stores
 template <bool SAMPLE, bool SPARES>
 GE_KERNEL ge_k_step_path64(GeParams P, const int64_t *actions_in, uint64_t policy_seed) {
   ge_wave_priority(GE_PRIO_STEP);
@@ -943,12 +944,8 @@ GE_KERNEL ge_k_step_path64(GeParams P, const int64_t *actions_in, uint64_t polic
     int64_t a64;
     if (SAMPLE) {
       const uint32_t cnt = (uint32_t)ge_popc64(mb);
-      if (!cnt || st == 1 || st == 4) a64 = -1;
-      else if (!GE_ON(8)) a64 = ge_ctz64(mb);
-      else {
-        uint64_t z = ge_mix64(policy_seed + (uint64_t)(P.env_index_base + i) * 0x9E3779B97F4A7C15ull + ts * 0xD1B54A32D192ED03ull);
-        a64 = ge_nth_set_bit(mb, (uint32_t)(((z >> 32) * (uint64_t)cnt) >> 32));
-      }
+      if (ge_policy_idle(cnt, st)) a64 = -1;
+      else a64 = ge_nth_set_bit(mb, ge_policy_draw(policy_seed, (uint64_t)(P.env_index_base + i), ts, cnt));
     } else {
       a64 = actions_in[i];
     }
@@ -956,7 +953,7 @@ GE_KERNEL ge_k_step_path64(GeParams P, const int64_t *actions_in, uint64_t polic
     const int a = in_range ? (int)a64 : 0;
     // ---- phase A, round 2: the record of the chosen node (its bit row and the weight codes of its 16 smallest neighbours)
     const int64_t nbase = (int64_t)i * n;
-    const ulonglong2 arec = GE_ON(4) ? ((const ulonglong2 *)G.node_rec)[nbase + a] : make_ulonglong2(mb * 3, 0x3333333333333333ull);
+    const ulonglong2 arec = ((const ulonglong2 *)G.node_rec)[nbase + a];
     const bool nbr = (arec.x >> head) & 1ull;                         // adjacency is symmetric
     const int rank = ge_popc64(arec.x & ((1ull << head) - 1ull));      // position of the head among a's neighbours
     int code = (int)((arec.y >> (4 * (rank & 15))) & 15ull);
@@ -1002,20 +999,18 @@ GE_KERNEL ge_k_step_path64(GeParams P, const int64_t *actions_in, uint64_t polic
 
     // ---- phase C: stores only
     ge_wait_loads();
-    if (GE_ON(64)) {
-      if (SAMPLE && G.actions_out) G.actions_out[i] = a64;
-      G.reward[i] = reward;
-      G.terminated[i] = (uint8_t)done;
-      G.invalid[i] = (uint8_t)invalid;
-      G.solved[i] = (int8_t)solved;
-    }
-    if ((acted || st == 3) && GE_ON(16))
+    if (SAMPLE && G.actions_out) G.actions_out[i] = a64;
+    G.reward[i] = reward;
+    G.terminated[i] = (uint8_t)done;
+    G.invalid[i] = (uint8_t)invalid;
+    G.solved[i] = (int8_t)solved;
+    if (acted || st == 3)
       ((ulonglong2 *)G.slot_rec)[i] = make_ulonglong2(ge_f64_as_u64(cost), ge_rec_make(moved ? a : head, st_out, dest, acted ? ((ts + 1) & 0xffffffffull) : ts));
     if (moved) {
-      if (GE_ON(1)) G.x[(nbase + a) * F + 0] = 1.f;
-      if (GE_ON(16)) G.node_bits[i] = vis;
+      G.x[(nbase + a) * F + 0] = 1.f;
+      G.node_bits[i] = vis;
     }
-    if (wrote_mask && GE_ON(16)) G.mask_bits[i] = nm;
+    if (wrote_mask) G.mask_bits[i] = nm;
     if constexpr (SPARES) { if (want_swap) P.spare_state[i] = 0; }
     if (fin) {
       G.final_cost[i] = cost;
@@ -1026,26 +1021,8 @@ GE_KERNEL ge_k_step_path64(GeParams P, const int64_t *actions_in, uint64_t polic
   flag[tid] = wrote_mask ? 1 : 0;
   ge_enqueue_reset<SPARES>(P, (int *)(flag + ge_bdim()), i0, i, tid, want_reset, want_swap);  // contains the barrier
   int nb = P.B - i0; if (nb > ge_bdim()) nb = ge_bdim();
-  if (nb <= 0 || !GE_ON(2)) return;
-  uint8_t *out = G.mask + (int64_t)i0 * n;
-  if ((n & 7) == 0) {
-    const int groups = nb * (n >> 3);
-    for (int g = tid; g < groups; g += ge_bdim()) {
-      const int e = (g << 3) / n, v0 = (g << 3) % n;
-      if (!flag[e]) continue;
-      const uint64_t b8 = (stage[e] >> v0) & 0xffull;
-      uint64_t y = (b8 * 0x0101010101010101ull) & 0x8040201008040201ull;
-      y = ((y + 0x7f7f7f7f7f7f7f7full) >> 7) & 0x0101010101010101ull;
-      *(uint64_t *)(out + ((int64_t)g << 3)) = y;
-    }
-  } else {
-    const int total = nb * n;
-    for (int idx = tid; idx < total; idx += ge_bdim()) {
-      const int e = idx / n, v = idx % n;
-      if (!flag[e]) continue;
-      out[idx] = (uint8_t)((stage[e] >> v) & 1ull);
-    }
-  }
+  if (nb <= 0) return;
+  ge_mask_slab_tail(G.mask + (int64_t)i0 * n, stage, 1, flag, nb, n, tid);
 }
 
 // DistributionCenter, n <= 64: the coverage range of the node each slot is about to choose, unless the row already exists

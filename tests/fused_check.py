@@ -5,9 +5,31 @@ ge_k_step_path64<true, ..> -- against the CPU oracle slot by slot, and against a
 The engine under test is driven ONLY by random_rollout(1, policy_seed); the action every slot must have drawn is
 oracle.policy_pick(oracle mask, policy_seed, global slot, executed transitions) and is read back from ge_buffers.actions_out."""
 import numpy as np
+import pytest
 import torch
 
 STRIDE, BASE, S0 = 7919, 11, 2**32 - 40  # seeds wrap around 2^32 inside the batch
+
+# (env id, kwargs, B, K, autoreset, prefetch, episodes required) -- the smallest shapes that take every branch of the pieces the step
+# kernels share (ge_policy_draw / ge_policy_idle, ge_bits8_to_bytes, ge_mask_slab_tail, ge_end_transition), run by the CPU harness and
+# by the GPU test alike.  B = 6: one partial workgroup, fewer slots than threads.  n = 10: mask rows of single bytes; n = 16: of whole
+# 8-byte groups.  Autoreset off runs until every slot has finished, K caps it.
+_SP, _MIS, _ST = "ShortestPath-v0", "MaxIndependentSet-v0", "SteinerTree-v0"
+_MIS10, _ST10 = dict(n_nodes=10, n_edges=20), dict(n_nodes=10, n_edges=20, n_dests=3, is_eval_env=True)
+SMALL_CASES = [
+    pytest.param(_SP, dict(n_nodes=10, n_edges=20, is_eval_env=True), 6, 40, True, 0, 6, id="small-path64-n10"),
+    pytest.param(_SP, dict(n_nodes=16, n_edges=32, is_eval_env=True), 6, 40, True, 2, 6, id="small-path64-n16-spares"),
+    pytest.param(_SP, dict(n_nodes=16, n_edges=32), 6, 40, "next_step", 0, 6, id="small-path64-n16-next-step"),
+    pytest.param(_MIS, _MIS10, 6, 40, True, 0, 6, id="small-mis-n10"),
+    pytest.param(_MIS, _MIS10, 6, 40, True, 3, 6, id="small-mis-n10-spares"),
+    pytest.param(_MIS, dict(_MIS10, n_nodes=16, n_edges=32), 6, 40, "next_step", 0, 6, id="small-mis-n16-next-step"),
+    pytest.param(_MIS, dict(_MIS10, n_nodes=16, n_edges=32), 6, 40, "next_step", 3, 6, id="small-mis-n16-next-step-spares"),
+    pytest.param(_MIS, _MIS10, 6, 40, False, 0, 6, id="small-mis-n10-autoreset-off"),
+    pytest.param(_ST, _ST10, 6, 40, True, 0, 6, id="small-quad-n10"),
+    pytest.param(_ST, _ST10, 6, 40, True, 3, 6, id="small-quad-n10-spares"),
+    pytest.param(_ST, _ST10, 6, 40, "next_step", 3, 6, id="small-quad-n10-next-step-spares"),
+    pytest.param(_ST, _ST10, 6, 40, False, 0, 6, id="small-quad-n10-autoreset-off"),
+]
 
 # slabs with one row (or n, or E rows) per slot that a frozen slot must leave untouched
 _SLOT_ROWS = ("x", "edge_attr", "mask", "mask_bits", "slot_rec", "node_bits", "target_bits", "counters", "terminals", "episode", "seed",

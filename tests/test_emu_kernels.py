@@ -11,6 +11,7 @@ import golden_util as gu
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "emu"))
 import build_emu  # noqa: E402
+import fused_check as fc  # noqa: E402
 import host_checks as hc  # noqa: E402
 
 import graphenvs_amd as ge  # noqa: E402
@@ -91,13 +92,17 @@ def _prefetch_rollout(emu, env_id, kw, B, K, period, autoreset=True, stride=1000
     env.reset(seed=5)
     refs = [oracle.OracleEnv(env_id, **kw) for _ in range(B)]
     eps, pend, swaps = [0] * B, [False] * B, 0
+    frozen, moves = [False] * B, [0] * B  # autoreset off: a finished slot stays as it is; moves of the running episode
     for i, r in enumerate(refs):
         r.reset(seed=5 + 3 + i)
     for k in range(K):
         a = env.sample_random_actions(policy_seed=9).clone().numpy()
-        valid = env.spare["state"].clone().numpy()
+        valid = env.spare["state"].clone().numpy() if env.spare is not None else [0] * B
         _, rew, term, _, info = env.step(a)
         for i, r in enumerate(refs):
+            if frozen[i]:
+                assert int(a[i]) == -1 and float(rew[i]) == 0 and not bool(term[i]), (k, i)
+                continue
             if pend[i]:  # next-step autoreset: this step regenerated the slot and ignored its action
                 eps[i] += 1
                 r.reset(seed=(5 + 3 + i + eps[i] * stride) % 2**32)
@@ -105,13 +110,19 @@ def _prefetch_rollout(emu, env_id, kw, B, K, period, autoreset=True, stride=1000
                 assert float(rew[i]) == 0 and not bool(term[i])
             else:
                 _, rr, dd, _, inf = r.step(int(a[i]))
+                moves[i] += 1
                 assert float(rew[i]) == rr and bool(term[i]) == dd, (k, i)
                 if dd:
                     assert float(info["solution_cost"][i]) == inf["solution_cost"]
                     assert float(info["heuristic_solution"][i]) == inf["heuristic_solution"]
+                    assert int(info["episode_length"][i]) == moves[i], (k, i)
+                    moves[i] = 0
                     swaps += int(valid[i])
                     if autoreset == "next_step":
                         pend[i] = True
+                    elif not autoreset:
+                        eps[i] += 1
+                        frozen[i] = True
                     else:
                         eps[i] += 1
                         r.reset(seed=(5 + 3 + i + eps[i] * stride) % 2**32)
@@ -131,10 +142,21 @@ def _prefetch_rollout(emu, env_id, kw, B, K, period, autoreset=True, stride=1000
     ("SteinerTree-v0", dict(n_nodes=12, n_edges=30, n_dests=3, is_eval_env=True), 5, 40, 5, True),
     ("DistributionCenter-v0", dict(n_nodes=12, n_edges=25), 5, 30, 2, True),
     ("ShortestPath-v0", dict(n_nodes=70, n_edges=160), 3, 36, 4, True),                    # generic feature kernel, feat_parts workgroups
+    # the end of a transition (ge_end_transition: final cost / length / baseline, reset or swap request, status) of ge_k_step and
+    # ge_k_step_edge: same-step and next-step autoreset with and without spares (period 0: none), and autoreset off
+    ("MaxIndependentSet-v0", dict(n_nodes=10, n_edges=20, weighted=False, is_eval_env=True), 6, 40, 0, True),
+    ("MaxIndependentSet-v0", dict(n_nodes=10, n_edges=20, weighted=False, is_eval_env=True), 6, 40, 3, True),
+    ("MaxIndependentSet-v0", dict(n_nodes=10, n_edges=20, weighted=False, is_eval_env=True), 6, 40, 0, "next_step"),
+    ("MaxIndependentSet-v0", dict(n_nodes=10, n_edges=20, weighted=False, is_eval_env=True), 6, 40, 3, "next_step"),
+    ("MaxIndependentSet-v0", dict(n_nodes=10, n_edges=20, weighted=False, is_eval_env=True), 6, 40, 0, False),
+    ("SteinerTree-v0", dict(n_nodes=10, n_edges=20, n_dests=3, is_eval_env=True), 6, 40, 0, True),
+    ("SteinerTree-v0", dict(n_nodes=10, n_edges=20, n_dests=3, is_eval_env=True), 6, 40, 3, "next_step"),
+    ("SteinerTree-v0", dict(n_nodes=10, n_edges=20, n_dests=3, is_eval_env=True), 6, 40, 0, "next_step"),
+    ("SteinerTree-v0", dict(n_nodes=10, n_edges=20, n_dests=3, is_eval_env=True), 6, 40, 0, False),
 ])
 def test_emulated_prefetch_matches_oracle(emu, env_id, kw, B, K, period, autoreset):
     episodes, swaps = _prefetch_rollout(emu, env_id, kw, B, K, period, autoreset)
-    assert episodes >= B and swaps > 0
+    assert episodes >= B and (swaps > 0 if period and autoreset else swaps == 0)
     if kw["n_nodes"] == 4:
         assert swaps < episodes  # both ways of getting the next episode ran: the image, and the regeneration in place
 
@@ -155,14 +177,15 @@ def test_emulated_fused_rollout_equals_sample_then_step(emu, env_id, kw):
     assert int(a.t["episode"].sum()) > 0
 
 
-@pytest.mark.parametrize("env_id,kw", [("SteinerTree-v0", dict(n_nodes=40, n_edges=100, n_dests=5)),    # A = 200, AW = 4: all four lanes of the quad
-                                       ("SteinerTree-v0", dict(n_nodes=64, n_edges=144, n_dests=6))])   # A = 288, AW = 5: a second chunk
-def test_emulated_fused_rollout_matches_oracle_and_unfused_twin(emu, env_id, kw):
+@pytest.mark.parametrize("env_id,kw,B,K,autoreset,prefetch,episodes", [
+    ("SteinerTree-v0", dict(n_nodes=40, n_edges=100, n_dests=5), 70, 40, True, 0, 1),    # A = 200, AW = 4: all four lanes of the quad
+    ("SteinerTree-v0", dict(n_nodes=64, n_edges=144, n_dests=6), 70, 40, True, 0, 1),    # A = 288, AW = 5: a second chunk
+    *fc.SMALL_CASES])
+def test_emulated_fused_rollout_matches_oracle_and_unfused_twin(emu, env_id, kw, B, K, autoreset, prefetch, episodes):
     """the quad sampler of ge_k_step_edge over mask rows of more than one word (its cross-lane exchanges run lane after lane here:
-    tests/test_gpu_fused_rollout.py runs the same body on the GPU)"""
-    import fused_check as fc
+    tests/test_gpu_fused_rollout.py runs the same body on the GPU), and the small shapes of fused_check.SMALL_CASES"""
     import oracle
-    fc.check_fused_vs_oracle(ge, oracle, "cpu", emu, env_id, kw, 70, 40)
+    fc.check_fused_vs_oracle(ge, oracle, "cpu", emu, env_id, kw, B, K, autoreset=autoreset, prefetch=prefetch, min_episodes=episodes)
 
 
 @pytest.mark.parametrize("env_id,sizes,common", [

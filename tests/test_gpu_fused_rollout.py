@@ -49,6 +49,7 @@ CASES = [
     pytest.param("DistributionCenter-v0", dict(n_nodes=100, n_edges=260, weighted=False), 300, 40, True, 0, 1, id="dc-w2"),
     # above 512 nodes: PRUNE 2, node sets in prune_scratch (no walk over 560 nodes ends within 20 steps)
     pytest.param("LongestPath-v0", dict(n_nodes=560, n_edges=1500, parenting=2), 6, 20, True, 0, 0, id="lp-p2-prune2"),
+    *fc.SMALL_CASES,
 ]
 
 

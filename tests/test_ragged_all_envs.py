@@ -50,6 +50,8 @@ CASES = [
     ("DistributionCenter-v0", [(2, 12, 25), (1, 64, 192, dict(max_distance=0.7)), (2, 65, 195)], dict(parenting=2), 12),
     ("PerishableProductDelivery-v0", [(2, 8, 12, dict(n_products=1)), (1, 64, 192), (2, 65, 195, dict(n_products=2))], dict(parenting=1), 16),
     ("MaxIndependentSet-v0", [(2, 8, 12), (1, 64, 192), (2, 65, 195)], dict(weighted=False, is_eval_env=True), 12),
+    # the second class's mask rows (13 bytes each) start at byte 15 of the mask slab: single bytes, one 8-byte store, single bytes
+    ("MaxIndependentSet-v0", [(3, 5, 7), (3, 13, 20)], dict(weighted=False, is_eval_env=True), 16),
 ]
 
 
