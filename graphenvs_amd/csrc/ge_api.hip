@@ -17,6 +17,7 @@
 #include "ge_step.h"
 #include "ge_tsp_eval.h"
 #include "ge_spare.h"
+#include "ge_policy.h"
 
 // An engine's launch geometry: filled once when the engine is created (finish_create), read by every launch, computed nowhere else.
 // The size classes of a multi-class engine are grouped into LDS buckets (by n_nodes: <= 128, <= 256, <= 512, larger), and the graph
@@ -37,6 +38,7 @@ struct GePlan {
   bool feat_fast;                       // a class takes the n <= 64 feature kernel (spatial TSP: float64 weights do not fit its LDS)
   int f64_lds, f64_pre_off, feat_grid;  // that kernel's launch; feat_grid without it: resident workgroups of the generic kernel at the largest class's carve
   GeLds inject;   // ge_inject_state runs the graph kernel on this carve (inject_carve)
+  int pol_group, pol_grid;  // policy head (ge_policy.h): lanes per row -- the power of two covering the widest mask row, 64 above 32 actions -- and workgroups
 };
 static int bucket_of(int n) { return n <= 128 ? 0 : (n <= 256 ? 1 : (n <= 512 ? 2 : 3)); }
 static bool takes_generic(const GeParams &C) { return C.n > 64 || C.spatial; }  // the class's slots run the generic feature kernel, not the fast path
@@ -51,6 +53,7 @@ struct GeKernels {
   void (*feat_combine)(GeParams, GeRagged, GeRun);
   void (*swap)(GeParams, GeRagged, GeRagged, ge_buffers, int);
   void (*sample)(GeParams, GeRagged, uint64_t, int64_t *);
+  void (*policy_head[3])(GeParams, GeRagged, GePolicyIO);  // [GE_POL_SAMPLE / GE_POL_GREEDY / GE_POL_EVALUATE]
   void (*dc_range)(GeParams, GeRagged, const int64_t *);
   void (*tsp_closure)(GeParams, GeRagged, int, uint8_t *, uint64_t, int);
   GeBaselineFn tsp_tour, mis_baseline, steiner_baseline;
@@ -296,6 +299,9 @@ static void select_kernels(ge_engine *e) {
   k.feat_combine = ge_k_feat_combine<RAGGED>;
   k.swap = ge_k_swap<RAGGED>;
   k.sample = ge_k_sample<RAGGED>;
+  k.policy_head[GE_POL_SAMPLE] = ge_k_policy_head<RAGGED, GE_POL_SAMPLE>;
+  k.policy_head[GE_POL_GREEDY] = ge_k_policy_head<RAGGED, GE_POL_GREEDY>;
+  k.policy_head[GE_POL_EVALUATE] = ge_k_policy_head<RAGGED, GE_POL_EVALUATE>;
   k.dc_range = ge_k_dc_range<RAGGED>;
   k.tsp_closure = ge_k_tsp_closure<RAGGED>;
   k.tsp_tour = ge_k_tsp_tour<RAGGED>;
@@ -393,6 +399,14 @@ static int finish_create(ge_engine *e) {
   if (!raise_lds((const void *)e->k.features, gen_lds)) return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the feature kernel");
   if (L.feat_fast && !raise_lds((const void *)e->k.features64, L.f64_lds)) return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the n<=64 feature kernel");
   L.feat_grid = resident_grid(L.feat_fast ? L.f64_lds : gen_body, P.B);
+  // ---- policy head: one lane group per row, the same width for every row of the launch (a slot finds its class through slot_class,
+  // so the rows a wave holds follow from the slot numbers alone); above 32 actions in any class a wave per row
+  int a_max = 0;
+  for (const GeParams *C = first; C < first + n_classes; C++) if (C->A > a_max) a_max = C->A;
+  L.pol_group = 4;
+  while (L.pol_group < 64 && L.pol_group < a_max) L.pol_group <<= 1;
+  const int64_t waves = ((int64_t)P.B * L.pol_group + GE_WAVE - 1) / GE_WAVE;
+  L.pol_grid = (int)((waves + GE_POL_THREADS / GE_WAVE - 1) / (GE_POL_THREADS / GE_WAVE));
   return GE_OK;
 }
 
@@ -412,6 +426,7 @@ extern "C" int ge_create(const ge_config *cfg, const ge_buffers *bufs, ge_engine
   return rc;
 }
 
+// (sizeof(GeParams) includes policy_off, the class's place in the policy head's flat logits)
 extern "C" int64_t ge_ragged_table_bytes(int32_t n_classes) { return (int64_t)sizeof(GeParams) * (n_classes > 0 ? n_classes : 0); }
 
 extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, int32_t n_classes, void *class_table,
@@ -426,6 +441,7 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
   e->classes.resize(n_classes);
   std::vector<int32_t> start(n_classes + 1, 0), cls_of((size_t)total);
   int widest = 0, aw_max = 0;
+  int64_t policy_off = 0;
   for (int c = 0; c < n_classes; c++) {
     GeParams &C = e->classes[c];
     int rc = derive(&cfgs[c], C, (int)total);
@@ -444,6 +460,7 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
       rc = fail(GE_E_BADARG, "reset_list, reset_count, work_list and work_count are engine-wide (the same pointers in every class), and slot_rec of class c starts at its first global slot");
     if (rc != GE_OK) return rc;
     C.buf = bufs[c];
+    C.policy_off = policy_off; policy_off += (int64_t)C.B * C.A;
     start[c + 1] = start[c] + cfgs[c].num_envs;
     for (int i = start[c]; i < start[c + 1]; i++) cls_of[(size_t)i] = c;
     if (C.n > e->classes[widest].n) widest = c;
@@ -476,6 +493,7 @@ extern "C" int ge_create_ragged(const ge_config *cfgs, const ge_buffers *bufs, i
   for (const GeParams &C : e->classes) if (C.feat_parts > e->P.feat_parts) e->P.feat_parts = C.feat_parts;
   e->P.buf = bufs[0];
   e->P.env_index_base = cfgs[0].env_index_base;
+  e->P.policy_off = 0;
   e->cfg = cfgs[0]; e->cfg.num_envs = (int32_t)total;
   e->n_classes = n_classes;
   e->aw_max = aw_max;
@@ -872,6 +890,36 @@ extern "C" int ge_sample_actions(ge_engine *e, uint64_t policy_seed, int64_t *ac
   int grid = (e->P.B + 255) / 256;
   GE_LAUNCH(e->k.sample, grid, 256, 0, stream, e->P, e->R, policy_seed, actions);
   return check_launch("sample kernel");
+}
+
+// ---- masked categorical policy head (ge_policy.h)
+static int launch_policy(ge_engine *e, int mode, GePolicyIO io, void *stream) {
+  io.group = e->plan.pol_group;
+  GE_LAUNCH(e->k.policy_head[mode], e->plan.pol_grid, GE_POL_THREADS, 0, stream, e->P, e->R, io);
+  return check_launch("policy head kernel");
+}
+
+extern "C" int ge_policy_sample(ge_engine *e, const float *logits, uint64_t policy_seed, int32_t greedy, int64_t *actions, float *logp,
+                                float *entropy, void *stream) {
+  if (!e || !logits || !actions) return fail(GE_E_BADARG, "null argument");
+  if (!e->loaded) return fail(GE_E_STATE, "the engine holds no episode yet: call ge_reset (or ge_inject_state) first");
+  const GePolicyIO io = {logits, nullptr, nullptr, actions, logp, entropy, policy_seed, 0};
+  return launch_policy(e, greedy ? GE_POL_GREEDY : GE_POL_SAMPLE, io, stream);
+}
+
+extern "C" int ge_policy_evaluate(ge_engine *e, const float *logits, const uint8_t *mask, const int64_t *actions, float *logp, float *entropy,
+                                  void *stream) {
+  if (!e || !logits || !mask || !actions) return fail(GE_E_BADARG, "null argument");
+  const GePolicyIO io = {logits, mask, actions, nullptr, logp, entropy, 0, 0};
+  return launch_policy(e, GE_POL_EVALUATE, io, stream);
+}
+
+extern "C" int ge_policy_step(ge_engine *e, const float *logits, uint64_t policy_seed, int32_t greedy, int64_t *actions, float *logp,
+                              float *entropy, void *stream) {
+  if (!e || !logits || !actions) return fail(GE_E_BADARG, "null argument");
+  int rc = check_state(e);  // (the guard of ge_step, before anything is launched)
+  if (rc == GE_OK) rc = ge_policy_sample(e, logits, policy_seed, greedy, actions, logp, entropy, stream);
+  return rc == GE_OK ? ge_step(e, actions, stream) : rc;
 }
 
 extern "C" int ge_random_rollout(ge_engine *e, uint64_t policy_seed, int32_t n_steps, int64_t *scratch, void *stream) {

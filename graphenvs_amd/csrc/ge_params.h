@@ -89,6 +89,8 @@ struct GeParams {
   uint8_t *spare_state;
   int32_t *swap_list, *swap_count;
   int32_t bucket;  // multi-class engine: the LDS bucket of this size class (ge_api.hip, GeBucket); 0 in a uniform engine
+  int64_t policy_off;  // multi-class engine: first element of this class's [B, A] block in the flat logits / mask of the policy head
+                       // (the sum of B * A over the classes in front of it: the packing of the classes' mask slabs); 0 in a uniform engine
 };
 
 // What a launch of the reset path does.  Decoded ONCE, on the host, from a validated request (ge_api.hip: run_*), so that the

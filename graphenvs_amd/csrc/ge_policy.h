@@ -1,0 +1,228 @@
+// Masked categorical policy head: logits in, {action, log-probability, entropy} of every slot out in ONE launch
+// (ge_policy_sample / ge_policy_evaluate / ge_policy_step, include/graphenvs.h).  Replaces, for a caller of the reference, the
+// masked_fill(~info['mask']) -> log_softmax -> sample -> gather -> entropy chain between the network and env.step().
+//
+// Arithmetic of a row (float32): mx = max of the valid logits, d = l - mx, w = expf(d) for valid actions and 0
+// otherwise, Z = sum w, logp[a] = d[a] - logf(Z), entropy = logf(Z) - (sum w d) / Z.  A row is worked on by one lane GROUP and
+// by nothing else: `group` lanes (a power of two, the same for every row of the launch), element j * group + g of the row in
+// lane g at chunk j.  Every sum is a fixed tree over (chunk, lane), so a row's result depends on the row alone -- not on the
+// batch size, the slot's place in the launch or its neighbours.
+//  - rows of at most 64 actions: group = the power of two covering the widest row, 64 / group rows per wave, one chunk;
+//  - longer rows: group = 64, a wave per row, coalesced chunks of 64.  Up to GE_POL_REG_CHUNKS chunks (2 048 actions, BASELINE
+//    config 4's row) the row is loaded ONCE and stays in registers between the max / sum pass and the prefix pass (expf is
+//    recomputed, w is not kept); a longer row is read twice: pass 1 keeps a running maximum and a sum rescaled under it per
+//    lane, pass 2 is the prefix pass.
+// Validity comes from the engine's mask_bits (sample, greedy: chunk j of a wave-wide row IS word j of the mask row; the [B, A]
+// bool slab is never read) or from the caller's bool bytes at the logits' own indices (evaluate).
+#pragma once
+#include <math.h>
+
+#include "ge_params.h"
+#include "ge_platform.h"
+#include "ge_step.h"
+
+enum { GE_POL_SAMPLE = 0, GE_POL_GREEDY = 1, GE_POL_EVALUATE = 2 };
+#define GE_POL_THREADS 256
+#define GE_POL_REG_CHUNKS 32  // chunks of a row held in registers: 64 * 32 = 2 048 actions
+#define GE_POL_BLOCK 8        // chunks a longer row loads back to back
+template <int N> struct GeInt { static constexpr int value = N; };
+
+struct GePolicyIO {
+  const float *logits;    // the classes' [B_c, A_c] blocks one after the other (GeParams.policy_off)
+  const uint8_t *mask;    // evaluate: bool bytes in the layout of logits
+  const int64_t *given;   // evaluate: the actions to score
+  int64_t *actions;       // sample, greedy
+  float *logp, *entropy;  // may be NULL
+  uint64_t policy_seed;
+  int32_t group;          // lanes per row (GePlan.pol_group)
+};
+
+// lane group of a row: lanes [lane - g, lane - g + G), G a power of two.  Every lane of the group executes these.
+GE_DEV float ge_shfl_f32(float v, int src) {
+  uint32_t u; __builtin_memcpy(&u, &v, 4);
+  u = ge_shfl_u32(u, src);
+  __builtin_memcpy(&v, &u, 4);
+  return v;
+}
+GE_DEV float ge_grp_max(float v, int lane, int G) { for (int o = G >> 1; o; o >>= 1) v = fmaxf(v, ge_shfl_f32(v, lane ^ o)); return v; }
+GE_DEV int ge_grp_max_i32(int v, int lane, int G) { for (int o = G >> 1; o; o >>= 1) { const int t = ge_shfl_i32(v, lane ^ o); v = t > v ? t : v; } return v; }
+// (a + b == b + a bit for bit: every lane of the group ends with the same sum)
+GE_DEV float ge_grp_sum(float v, int lane, int G) { for (int o = G >> 1; o; o >>= 1) v += ge_shfl_f32(v, lane ^ o); return v; }
+// inclusive prefix over the lanes of the group
+GE_DEV float ge_grp_prefix(float v, int lane, int G) {
+  const int g = lane & (G - 1);
+  for (int o = 1; o < G; o <<= 1) { const float t = ge_shfl_f32(v, g >= o ? lane - o : lane); if (g >= o) v += t; }
+  return v;
+}
+// the group's lanes of a ballot, lane g of the group in bit g
+GE_DEV uint64_t ge_grp_ballot(bool p, int lane, int G) {
+  const uint64_t b = ge_ballot(p) >> (lane & ~(G - 1));
+  return G == 64 ? b : (b & ((1ull << G) - 1ull));
+}
+
+// One chunk of the prefix pass.  xj / v: this lane's logit and its validity; mx, t: the row's maximum and u * Z.
+// s1 gathers w * d; act (-1: not found yet) the sampled / greedy action, carry the prefix in front of the chunk.
+template <int MODE>
+GE_DEV void ge_pol_chunk(float xj, bool v, int first, float mx, float t, int lane, int G, float &s1, float &carry, int &act) {
+  const float d = v ? xj - mx : 0.0f, w = v ? expf(d) : 0.0f;
+  s1 += w * d;
+  if (MODE == GE_POL_EVALUATE || act >= 0) return;  // (act is the same in every lane of the group)
+  if (MODE == GE_POL_GREEDY) {
+    const uint64_t hit = ge_grp_ballot(v && xj == mx, lane, G);
+    if (hit) act = first + ge_ctz64(hit);
+    return;
+  }
+  const float p = carry + ge_grp_prefix(w, lane, G);
+  const uint64_t hit = ge_grp_ballot(v && p > t, lane, G);
+  if (hit) act = first + ge_ctz64(hit);
+  else carry = ge_shfl_f32(p, (lane | (G - 1)));
+}
+
+template <bool RAGGED, int MODE>
+GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePolicyIO io) {
+  const int tid = ge_tid(), lane = tid & 63;
+  const int G = io.group, g = lane & (G - 1), gbase = lane - g;
+  const int64_t item = (int64_t)ge_bid() * (GE_POL_THREADS / 64) + (tid >> 6);  // this wave's 64 / G rows
+  const int64_t slot = item * (64 / G) + (lane - g) / G;
+  if (slot >= PG.B) return;  // (whole groups leave: a group never straddles rows)
+  const int ig = (int)slot;
+  int cls = 0, lo = 0;
+  if constexpr (RAGGED) {
+    cls = R.slot_class[ig];
+    if (G == 64) cls = (int)ge_uniform_u32((uint32_t)cls);
+    lo = R.class_start[cls];
+  }
+  const GeParams &P = RAGGED ? R.classes[cls] : PG;
+  const int i = ig - lo, A = P.A, AW = P.AW;
+  const int64_t row = P.policy_off + (int64_t)i * A;
+  const float *x = io.logits + row;
+  const uint8_t *mbytes = MODE == GE_POL_EVALUATE ? io.mask + row : nullptr;
+  const uint64_t *mb = P.buf.mask_bits + (int64_t)i * AW;
+  const int nch = G < 64 ? 1 : (A + 63) >> 6;  // (G < 64: every row of the launch fits its group)
+  // mask words j0 .. j0 + G - 1 of the row, word j0 + g in lane g: one unconditional load (a word past the end re-reads word 0)
+  auto words_at = [&](int j0) { return mb[j0 + g < AW ? j0 + g : 0]; };
+  const bool writer = g == 0;
+  uint64_t packed = 0;
+  if (MODE != GE_POL_EVALUATE) packed = P.buf.slot_rec[2 * (int64_t)i + 1];
+
+  float mx = -INFINITY, Z = 0.0f, s1 = 0.0f, carry = 0.0f, t = 0.0f;
+  int act = -1, last = -1;  // last: the highest valid action of this lane
+  bool any;
+  auto threshold = [&]() {  // the draw of this slot and step: the key of ge_policy_draw
+    const uint64_t z = ge_mix64(io.policy_seed + (uint64_t)(P.env_index_base + i) * 0x9E3779B97F4A7C15ull + ge_rec_tstep(packed) * 0xD1B54A32D192ED03ull);
+    return ((float)(z >> 40) * 0x1p-24f) * Z;
+  };
+  const bool frozen = MODE != GE_POL_EVALUATE && ge_policy_idle(1u, ge_rec_status(packed));
+  // ---- the row in registers.  NCH, the row's chunk count rounded up to a power of two, is a compile-time constant: the loops
+  // unroll fully, xv[] is indexed statically and the NCH loads (a chunk past the row re-reads element 0) are issued back to back
+  // in front of the first use.
+  auto in_regs = [&](auto nc) {
+    constexpr int NCH = decltype(nc)::value;
+    float xv[NCH];
+    uint8_t mv[NCH];
+    uint32_t vb = 0;  // bit j: element j * G + g is a valid action
+    uint64_t words = 0;
+    if (MODE != GE_POL_EVALUATE) words = words_at(0);
+#pragma unroll
+    for (int j = 0; j < NCH; j++) {
+      const int idx = j * G + g;
+      xv[j] = x[idx < A ? idx : 0];
+      if (MODE == GE_POL_EVALUATE) mv[j] = mbytes[idx < A ? idx : 0];
+    }
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NCH; j++) {
+      const int idx = j * G + g;
+      bool v;  // (every lane of the group takes part in the shuffle, also one past the row's end)
+      if (MODE == GE_POL_EVALUATE) v = idx < A && mv[j] != 0;
+      else { const uint64_t mw = ge_shfl_u64(words, gbase + j); v = idx < A && ((mw >> (idx & 63)) & 1ull) != 0ull; }
+      vb |= (uint32_t)v << j;
+      if (v) m = fmaxf(m, xv[j]);
+    }
+    mx = ge_grp_max(m, lane, G);
+    any = ge_grp_ballot(vb != 0u, lane, G) != 0ull;
+    if (!any || frozen) return;
+    float s = 0.0f;
+#pragma unroll
+    for (int j = 0; j < NCH; j++)
+      if ((vb >> j) & 1u) s += expf(xv[j] - mx);
+    Z = ge_grp_sum(s, lane, G);
+    if (MODE == GE_POL_SAMPLE) t = threshold();
+#pragma unroll
+    for (int j = 0; j < NCH; j++)
+      if (j < nch) ge_pol_chunk<MODE>(xv[j], ((vb >> j) & 1u) != 0u, j * G, mx, t, lane, G, s1, carry, act);
+    if (vb) last = (31 - ge_clz32(vb)) * G + g;
+  };
+  if (nch <= 1) in_regs(GeInt<1>());
+  else if (nch <= 2) in_regs(GeInt<2>());
+  else if (nch <= 4) in_regs(GeInt<4>());
+  else if (nch <= 8) in_regs(GeInt<8>());
+  else if (nch <= 16) in_regs(GeInt<16>());
+  else if (nch <= GE_POL_REG_CHUNKS) in_regs(GeInt<GE_POL_REG_CHUNKS>());
+  else {
+    // ---- a row above 2 048 actions (a wave per row): read twice, GE_POL_BLOCK chunks loaded back to back at a time
+    float m = -INFINITY, s = 0.0f;
+    uint64_t words = 0;
+    bool seen = false;
+    float xs[GE_POL_BLOCK];
+    uint8_t ms[GE_POL_BLOCK];
+    auto load_block = [&](int j0) {  // (a chunk past the row re-reads element 0 and counts as invalid)
+      if (MODE != GE_POL_EVALUATE && (j0 & 63) == 0) words = words_at(j0);
+#pragma unroll
+      for (int k = 0; k < GE_POL_BLOCK; k++) {
+        const int idx = (j0 + k) * 64 + lane;
+        xs[k] = x[idx < A ? idx : 0];
+        if (MODE == GE_POL_EVALUATE) ms[k] = mbytes[idx < A ? idx : 0];
+      }
+    };
+    auto valid_at = [&](int j0, int k) {
+      const int idx = (j0 + k) * 64 + lane;
+      if (MODE == GE_POL_EVALUATE) return idx < A && ms[k] != 0;
+      const uint64_t mw = ge_shfl_u64(words, (j0 + k) & 63);  // (every lane takes part, also one past the row's end)
+      return idx < A && ((mw >> (idx & 63)) & 1ull) != 0ull;
+    };
+    for (int j0 = 0; j0 < nch; j0 += GE_POL_BLOCK) {
+      load_block(j0);
+#pragma unroll
+      for (int k = 0; k < GE_POL_BLOCK; k++) {
+        const float xj = xs[k];
+        if (valid_at(j0, k)) {
+          if (xj > m) { s = s * expf(m - xj) + 1.0f; m = xj; }  // (first element: 0 * expf(-inf) + 1)
+          else s += expf(xj - m);
+          seen = true; last = (j0 + k) * 64 + lane;
+        }
+      }
+    }
+    mx = ge_grp_max(m, lane, G);
+    any = ge_grp_ballot(seen, lane, G) != 0ull;
+    if (any && !frozen) {
+      Z = ge_grp_sum(seen ? s * expf(m - mx) : 0.0f, lane, G);
+      if (MODE == GE_POL_SAMPLE) t = threshold();
+      for (int j0 = 0; j0 < nch; j0 += GE_POL_BLOCK) {
+        load_block(j0);
+#pragma unroll
+        for (int k = 0; k < GE_POL_BLOCK; k++)
+          if (j0 + k < nch) ge_pol_chunk<MODE>(xs[k], valid_at(j0, k), (j0 + k) * 64, mx, t, lane, G, s1, carry, act);
+      }
+    }
+  }
+  const bool idle = !any || frozen;
+  float lp = 0.0f, ent = 0.0f;
+  if (!idle) {
+    const float S1 = ge_grp_sum(s1, lane, G), lz = logf(Z);
+    ent = lz - S1 / Z;
+    // rounding left no prefix above t: the last valid action (greedy: only non-finite logits get here; x[act] stays inside the row)
+    if (MODE != GE_POL_EVALUATE && act < 0) act = ge_grp_max_i32(last, lane, G);
+  }
+  if (!writer) return;
+  if (MODE == GE_POL_EVALUATE) {
+    const int64_t a = io.given[ig];
+    const bool ok = !idle && a >= 0 && a < (int64_t)A && mbytes[a] != 0;
+    lp = ok ? (x[a] - mx) - logf(Z) : -INFINITY;
+  } else {
+    if (!idle) lp = (x[act] - mx) - logf(Z);
+    io.actions[ig] = idle ? -1 : (int64_t)act;
+  }
+  if (io.logp) io.logp[ig] = lp;
+  if (io.entropy) io.entropy[ig] = ent;
+}

@@ -136,6 +136,19 @@ class MixedVectorEnv:
     def sample_random_actions(self, policy_seed=0):
         return self._each(lambda m: m.sample_random_actions(policy_seed))
 
+    def sample_actions(self, logits, policy_seed=0, greedy=False):
+        """EngineHandle.sample_actions of every member: one logits tensor per member in, one (actions, logp, entropy) per member out"""
+        return self._each(lambda m, x: m.sample_actions(x, policy_seed, greedy), logits)
+
+    def evaluate_actions(self, logits, actions, mask):
+        """EngineHandle.evaluate_actions of every member: one (logp, entropy) per member"""
+        return self._each(lambda m, a: m.evaluate_actions(*a), list(zip(logits, actions, mask)))
+
+    def step_policy(self, logits, policy_seed=0, greedy=False):
+        """EngineHandle.step_policy of every member, returned like step(): one list per element of the step tuple"""
+        outs = self._each(lambda m, x: m.step_policy(x, policy_seed, greedy), logits)
+        return tuple(list(col) for col in zip(*outs))
+
     def random_rollout(self, n_steps, policy_seed=0):
         """n_steps fused (device policy + step + autoreset) vector steps of every member.  The members are independent engines and
         nothing is read in between, so the streams are forked ONCE, the launches of the members alternate step by step (the host

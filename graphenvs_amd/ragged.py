@@ -173,8 +173,16 @@ class RaggedVectorEnv(EngineHandle):
         assert actions.shape == (self.num_envs,) and self._was_reset
         self._act_keepalive = actions
         self._call("ge_step", actions.data_ptr(), self._stream())
-        g = self.g
-        return self.graph(), g["reward"], g["terminated"].view(torch.bool), self._truncated, self._info(True)
+        return self._after_step()
+
+    def _policy_numel(self):
+        return self.mask_flat.numel()  # the classes' [B_c, A_c] blocks one after the other: logits go in in this layout
+
+    def _after_step(self, extra=None):
+        g, info = self.g, self._info(True)
+        if extra:
+            info.update(extra)
+        return self.graph(), g["reward"], g["terminated"].view(torch.bool), self._truncated, info
 
     def flat_obs(self):
         """utils.vectorize_graph of every slot, one [B_c, obs_len_c] tensor per class (views of one buffer)."""

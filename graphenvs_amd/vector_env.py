@@ -184,9 +184,11 @@ def slot_seeds(seed, num_envs, env_index_base, device):
 
 class EngineHandle:
     """What owns a ge_* handle: ``_L`` the library, ``_h`` the handle, ``device``, and the calls that are the same for a uniform
-    and a multi-class engine.  A subclass sets those three and ``_actions_scratch`` (int64, one entry per slot)."""
+    and a multi-class engine.  A subclass sets those three, ``num_envs`` and ``_actions_scratch`` (int64, one entry per slot), and
+    implements ``_policy_numel()`` and ``_after_step(extra)`` for the policy head."""
     _h = None
     _flat = None
+    _policy = None
 
     def _stream(self):
         if self.device.type == "cuda":
@@ -224,6 +226,71 @@ class EngineHandle:
         out = self._actions_scratch if out is None else out
         self._call("ge_sample_actions", int(policy_seed), out.data_ptr(), self._stream())
         return out
+
+    # ------------------------------------------------------------------ masked categorical policy head (ge_policy_*)
+    def _policy_input(self, v, what, dtypes):
+        """`v` as a contiguous tensor of this engine's device with one element per (slot, action)"""
+        if not torch.is_tensor(v):
+            raise TypeError(f"{what} must be a torch tensor, got {type(v).__name__}")
+        if v.dtype not in dtypes:
+            raise TypeError(f"{what} must be {' or '.join(str(d) for d in dtypes)}, got {v.dtype}")
+        if v.device.type != self.device.type or (self.device.index is not None and v.device.index != self.device.index):
+            raise ValueError(f"{what} is on {v.device}, the engine on {self.device}")
+        if v.numel() != self._policy_numel():
+            raise ValueError(f"{what} has {v.numel()} elements, the engine's mask {self._policy_numel()} (one per slot and action)")
+        return v.contiguous()
+
+    def _policy_buffers(self):
+        if self._policy is None:
+            f = lambda dt: torch.empty(self.num_envs, dtype=dt, device=self.device)
+            self._policy = dict(actions=f(torch.int64), logp=f(torch.float32), entropy=f(torch.float32),
+                                eval_logp=f(torch.float32), eval_entropy=f(torch.float32))
+        return self._policy
+
+    def sample_actions(self, logits, policy_seed=0, greedy=False):
+        """Masked categorical draw of every slot from the caller's logits, in one launch: ``(actions int64 [B], logp float32 [B],
+        entropy float32 [B])`` -- what ``Categorical(logits=logits.masked_fill(~info['mask'], -inf))`` gives through sample(),
+        log_prob() and entropy().  ``logits``: any float32 tensor on the engine's device with one element per (slot, action) in the
+        layout of ``info['mask']`` (a multi-class engine: of ``mask_flat``): [B, A], [B * n] and [B * n, 1] are all accepted, a
+        wrong element count, dtype or device raises.  The draw is a function of (policy_seed, global slot, the slot's transition
+        count); ``greedy=True`` takes the valid action of largest logit.  A slot with no valid action and a frozen slot return
+        -1, 0, 0.  The three tensors are allocated once per engine and overwritten by the next sample_actions() / step_policy():
+        ``.clone()`` what a rollout buffer keeps, as with step()."""
+        x = self._policy_input(logits, "logits", (torch.float32,))
+        o = self._policy_buffers()
+        self._policy_keepalive = x
+        self._call("ge_policy_sample", x.data_ptr(), int(policy_seed), int(bool(greedy)), o["actions"].data_ptr(), o["logp"].data_ptr(),
+                   o["entropy"].data_ptr(), self._stream())
+        return o["actions"], o["logp"], o["entropy"]
+
+    def evaluate_actions(self, logits, actions, mask):
+        """``(logp, entropy)`` of stored ``actions`` [B] under stored masks: the re-scoring of a PPO / A2C update.  ``mask``: bool or
+        uint8, one element per logit -- what info['mask'] (``mask_flat``) held when the actions were drawn, cloned into the rollout
+        buffer; the engine's live mask is not read.  On the logits, mask and actions of a sample_actions() call it returns that
+        call's logp and entropy bit for bit.  An action of -1, out of range or masked out gives -inf.  The two tensors are
+        allocated once per engine and overwritten by the next evaluate_actions()."""
+        x = self._policy_input(logits, "logits", (torch.float32,))
+        mk = self._policy_input(mask, "mask", (torch.bool, torch.uint8)).view(torch.uint8)
+        if not torch.is_tensor(actions):
+            actions = torch.as_tensor(np.asarray(actions, dtype=np.int64))
+        a = actions.to(device=self.device, dtype=torch.int64).contiguous()
+        assert a.shape == (self.num_envs,)
+        o = self._policy_buffers()
+        self._evaluate_keepalive = (x, mk, a)
+        self._call("ge_policy_evaluate", x.data_ptr(), mk.data_ptr(), a.data_ptr(), o["eval_logp"].data_ptr(), o["eval_entropy"].data_ptr(),
+                   self._stream())
+        return o["eval_logp"], o["eval_entropy"]
+
+    def step_policy(self, logits, policy_seed=0, greedy=False):
+        """sample_actions(logits, ...) and step() of the drawn actions in one call, nothing read back in between: returns what
+        step() returns, with ``info['action']``, ``info['logp']`` and ``info['entropy']`` added (the tensors of sample_actions)."""
+        x = self._policy_input(logits, "logits", (torch.float32,))
+        assert self._was_reset, "call reset() (or inject_state()) before step_policy()"
+        o = self._policy_buffers()
+        self._policy_keepalive = x
+        self._call("ge_policy_step", x.data_ptr(), int(policy_seed), int(bool(greedy)), o["actions"].data_ptr(), o["logp"].data_ptr(),
+                   o["entropy"].data_ptr(), self._stream())
+        return self._after_step(dict(action=o["actions"], logp=o["logp"], entropy=o["entropy"]))
 
     def random_rollout(self, n_steps, policy_seed=0):
         self._call("ge_random_rollout", int(policy_seed), int(n_steps), self._actions_scratch.data_ptr(), self._stream())
@@ -469,11 +536,21 @@ class VectorGraphEnv(EngineHandle, _VectorBase):
         assert self._was_reset, "call reset() (or inject_state()) before step()"
         self._act_keepalive = actions
         self._call("ge_step", actions.data_ptr(), self._stream())
+        return self._after_step()
+
+    def _policy_numel(self):
+        return self.num_envs * self.A
+
+    def _after_step(self, extra=None):
+        """what step() returns once the step is launched (`extra`: more entries of info)"""
         t = self.t
         if self.strict and bool(t["invalid"].any()):
             bad = torch.nonzero(t["invalid"]).flatten().tolist()
             raise AssertionError(f"invalid action in slots {bad[:8]} (the reference asserts here)")
-        out = (self._obs(), t["reward"], t["terminated"].view(torch.bool), self._truncated, self._info(True))
+        info = self._info(True)
+        if extra:
+            info.update(extra)
+        out = (self._obs(), t["reward"], t["terminated"].view(torch.bool), self._truncated, info)
         return self._copied(out) if self.copy_outputs else out
 
     # ------------------------------------------------------------------ extras

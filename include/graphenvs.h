@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define GE_ABI_VERSION 5
+#define GE_ABI_VERSION 6
 
 /* env ids of graph_envs/__init__.py:9-56 that are on the hot path */
 enum {
@@ -273,6 +273,37 @@ int ge_vectorize(ge_engine *e, float *out, void *stream);
 /* Uniform random valid action per slot from mask_bits (bench/test policy; the same function is
  * restated in oracle/ge_oracle.c oge_policy_pick).  actions [B] int64; -1 where the mask is empty. */
 int ge_sample_actions(ge_engine *e, uint64_t policy_seed, int64_t *actions, void *stream);
+
+/* Masked categorical policy head: the caller's network emits logits, the engine owns the masks.  One launch replaces what a caller
+ * of the reference writes between the network and env.step() -- logits.masked_fill(~info['mask'], -inf), log_softmax, a draw,
+ * gather for the log-probability, the entropy -- and, for a multi-class engine, the per-graph segment softmax over a PyG Batch.
+ *  - logits: float32, contiguous; a uniform engine takes [B, A] (A = ge_layout.A), a multi-class engine the classes' [B_c, A_c]
+ *    blocks one after the other, class c starting at element sum_{c' < c} B_c' * A_c' (the packing of the classes' mask slabs, and
+ *    the class order of ge_vectorize).  Finite values are the caller's contract;
+ *  - per row, in float32: mx = max of the valid logits, d = l - mx, w = expf(d) (0 for invalid actions), Z = sum w,
+ *    logp[a] = d[a] - logf(Z), entropy = logf(Z) - (sum w d) / Z.  A row's result depends on the row alone (not on the batch size or
+ *    the slot's place in it): shards and ranks reproduce the unsharded run bit for bit;
+ *  - greedy == 0: u = (z >> 40) * 2^-24 with z the 64-bit draw ge_sample_actions keys by (policy_seed, env_index_base + slot, the
+ *    slot's transition count); the action is the first valid one, ascending, whose inclusive prefix sum of w exceeds u * Z (the last
+ *    valid action if rounding leaves none).  greedy != 0: the valid action of largest logit, lowest index on ties;
+ *  - actions [B] int64 (required), logp [B] and entropy [B] float32 (either may be NULL);
+ *  - a slot with an empty mask row and a frozen slot (status 1 or 4) get action -1, logp 0, entropy 0, like ge_sample_actions.
+ * Validity is read from mask_bits; GE_E_STATE before the first ge_reset / ge_inject_state (there is no mask yet). */
+int ge_policy_sample(ge_engine *e, const float *logits, uint64_t policy_seed, int32_t greedy,
+                     int64_t *actions, float *logp, float *entropy, void *stream);
+
+/* Re-score stored actions under stored masks -- the new_logp / entropy of a PPO or A2C update (Categorical(logits=masked).log_prob(a),
+ * .entropy() for a caller of the reference).  mask: bool bytes in the layout of logits, i.e. what ge_buffers.mask held when the
+ * actions were drawn and a rollout buffer kept; the engine's live mask is not read and no episode is needed.  Same arithmetic as
+ * ge_policy_sample: on the logits, mask and actions of such a call it returns that call's logp and entropy bit for bit.  An action
+ * of -1, outside [0, A) or with a zero mask byte gives logp = -inf; the entropy is the row's, 0 for an all-zero row. */
+int ge_policy_evaluate(ge_engine *e, const float *logits, const uint8_t *mask, const int64_t *actions,
+                       float *logp, float *entropy, void *stream);
+
+/* ge_policy_sample followed by ge_step(actions) on `stream`, without the host in between: one call per step of a training rollout.
+ * Same call-order guard as ge_step. */
+int ge_policy_step(ge_engine *e, const float *logits, uint64_t policy_seed, int32_t greedy,
+                   int64_t *actions, float *logp, float *entropy, void *stream);
 
 /* n_steps x (sample, step[, autoreset]) without host involvement between launches.  actions_scratch [B] int64 is
  * only needed by env types without a fused policy+step kernel (it may be NULL otherwise). */
