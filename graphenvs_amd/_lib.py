@@ -97,7 +97,7 @@ SYMBOLS = [
     "ge_abi_version", "ge_get_layout", "ge_create", "ge_destroy", "ge_ragged_table_bytes", "ge_create_ragged", "ge_reset", "ge_step", "ge_step_only",
     "ge_reset_pending", "ge_reset_continue", "ge_inject_state", "ge_mark_restored", "ge_vectorize", "ge_sample_actions", "ge_random_rollout",
     "ge_timed_rollout", "ge_timed_step_burst", "ge_timed_empty_burst", "ge_last_error", "ge_source_hash", "ge_attach_spares",
-    "ge_policy_sample", "ge_policy_evaluate", "ge_policy_step",
+    "ge_policy_sample", "ge_policy_evaluate", "ge_policy_step", "ge_policy_backward",
 ]
 
 
@@ -196,6 +196,8 @@ def bind(lib):
         getattr(lib, name).argtypes = [vp, vp, u64, i32, vp, vp, vp, vp]
     lib.ge_policy_evaluate.restype = C.c_int
     lib.ge_policy_evaluate.argtypes = [vp, vp, vp, vp, vp, vp, vp]  # (logits, mask, actions, logp, entropy, stream)
+    lib.ge_policy_backward.restype = C.c_int
+    lib.ge_policy_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]  # (logits, mask, actions, grad_logp, grad_entropy, grad_logits, stream)
     lib.ge_random_rollout.restype = C.c_int
     lib.ge_random_rollout.argtypes = [vp, u64, i32, vp, vp]
     lib.ge_timed_rollout.restype = C.c_int
@@ -216,7 +218,7 @@ def bind(lib):
 _lib = None
 
 
-ABI_VERSION = 6  # GE_ABI_VERSION of include/graphenvs.h this host was written against
+ABI_VERSION = 7  # GE_ABI_VERSION of include/graphenvs.h this host was written against
 
 
 def load():

@@ -53,7 +53,8 @@ struct GeKernels {
   void (*feat_combine)(GeParams, GeRagged, GeRun);
   void (*swap)(GeParams, GeRagged, GeRagged, ge_buffers, int);
   void (*sample)(GeParams, GeRagged, uint64_t, int64_t *);
-  void (*policy_head[3])(GeParams, GeRagged, GePolicyIO);  // [GE_POL_SAMPLE / GE_POL_GREEDY / GE_POL_EVALUATE]
+  void (*policy_head[GE_POL_MODES])(GeParams, GeRagged, GePolicyIO);  // [GE_POL_SAMPLE / GE_POL_GREEDY / GE_POL_EVALUATE]
+  void (*policy_grad)(GeParams, GeRagged, GePolicyIO);     // the logits gradient of GE_POL_EVALUATE's outputs
   void (*dc_range)(GeParams, GeRagged, const int64_t *);
   void (*tsp_closure)(GeParams, GeRagged, int, uint8_t *, uint64_t, int);
   GeBaselineFn tsp_tour, mis_baseline, steiner_baseline;
@@ -302,6 +303,7 @@ static void select_kernels(ge_engine *e) {
   k.policy_head[GE_POL_SAMPLE] = ge_k_policy_head<RAGGED, GE_POL_SAMPLE>;
   k.policy_head[GE_POL_GREEDY] = ge_k_policy_head<RAGGED, GE_POL_GREEDY>;
   k.policy_head[GE_POL_EVALUATE] = ge_k_policy_head<RAGGED, GE_POL_EVALUATE>;
+  k.policy_grad = ge_k_policy_grad<RAGGED>;
   k.dc_range = ge_k_dc_range<RAGGED>;
   k.tsp_closure = ge_k_tsp_closure<RAGGED>;
   k.tsp_tour = ge_k_tsp_tour<RAGGED>;
@@ -892,11 +894,16 @@ extern "C" int ge_sample_actions(ge_engine *e, uint64_t policy_seed, int64_t *ac
   return check_launch("sample kernel");
 }
 
-// ---- masked categorical policy head (ge_policy.h)
-static int launch_policy(ge_engine *e, int mode, GePolicyIO io, void *stream) {
+// ---- masked categorical policy head (ge_policy.h): the forward modes and the gradient kernel, launched here in one geometry
+static int launch_policy_kernel(ge_engine *e, void (*kernel)(GeParams, GeRagged, GePolicyIO), const char *what, GePolicyIO io, void *stream) {
   io.group = e->plan.pol_group;
-  GE_LAUNCH(e->k.policy_head[mode], e->plan.pol_grid, GE_POL_THREADS, 0, stream, e->P, e->R, io);
-  return check_launch("policy head kernel");
+  GE_LAUNCH(kernel, e->plan.pol_grid, GE_POL_THREADS, 0, stream, e->P, e->R, io);
+  return check_launch(what);
+}
+static int launch_policy(ge_engine *e, int mode, GePolicyIO io, void *stream) {  // mode: GE_POL_SAMPLE / GREEDY / EVALUATE
+  static_assert(GE_POL_GRAD >= GE_POL_MODES, "the gradient is no entry of policy_head");
+  if (mode < 0 || mode >= GE_POL_MODES) return fail(GE_E_BADARG, "no such policy head mode");
+  return launch_policy_kernel(e, e->k.policy_head[mode], "policy head kernel", io, stream);
 }
 
 extern "C" int ge_policy_sample(ge_engine *e, const float *logits, uint64_t policy_seed, int32_t greedy, int64_t *actions, float *logp,
@@ -912,6 +919,13 @@ extern "C" int ge_policy_evaluate(ge_engine *e, const float *logits, const uint8
   if (!e || !logits || !mask || !actions) return fail(GE_E_BADARG, "null argument");
   const GePolicyIO io = {logits, mask, actions, nullptr, logp, entropy, 0, 0};
   return launch_policy(e, GE_POL_EVALUATE, io, stream);
+}
+
+extern "C" int ge_policy_backward(ge_engine *e, const float *logits, const uint8_t *mask, const int64_t *actions, const float *grad_logp,
+                                  const float *grad_entropy, float *grad_logits, void *stream) {
+  if (!e || !logits || !mask || !actions || !grad_logits) return fail(GE_E_BADARG, "null argument");
+  const GePolicyIO io = {logits, mask, actions, nullptr, nullptr, nullptr, 0, 0, grad_logp, grad_entropy, grad_logits};
+  return launch_policy_kernel(e, e->k.policy_grad, "policy gradient kernel", io, stream);
 }
 
 extern "C" int ge_policy_step(ge_engine *e, const float *logits, uint64_t policy_seed, int32_t greedy, int64_t *actions, float *logp,

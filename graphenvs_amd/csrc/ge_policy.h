@@ -13,7 +13,14 @@
 //    recomputed, w is not kept); a longer row is read twice: pass 1 keeps a running maximum and a sum rescaled under it per
 //    lane, pass 2 is the prefix pass.
 // Validity comes from the engine's mask_bits (sample, greedy: chunk j of a wave-wide row IS word j of the mask row; the [B, A]
-// bool slab is never read) or from the caller's bool bytes at the logits' own indices (evaluate).
+// bool slab is never read) or from the caller's bool bytes at the logits' own indices (evaluate, gradient).
+//
+// Gradient (ge_policy_backward, ge_k_policy_grad): the same row pass -- ge_pol_rows, the body of both kernels -- in the geometry of
+// the forward, then, with p = w / Z, lp = d - logf(Z), H the entropy and the upstream gradients gl (of logp) and gh (of entropy),
+//   grad[a] = gl ([a == a*] - p[a]) - gh p[a] (lp[a] + H)  for a valid a,  0.0 for a masked one;
+// gl counts as 0 where the action a* is -1, out of range or masked out (the forward's logp is -inf there).  A row held in registers
+// is stored from them, chunk after chunk (4 B of logit and 1 B of mask read, 4 B written per element); a longer row is read a
+// third time.  Every element of every row is written; lanes and chunks past the row's end store nothing.
 #pragma once
 #include <math.h>
 
@@ -21,7 +28,8 @@
 #include "ge_platform.h"
 #include "ge_step.h"
 
-enum { GE_POL_SAMPLE = 0, GE_POL_GREEDY = 1, GE_POL_EVALUATE = 2 };
+// forward modes (the GE_POL_MODES entries of GeKernels.policy_head), then the gradient: ge_k_policy_grad, no entry of that table
+enum { GE_POL_SAMPLE = 0, GE_POL_GREEDY = 1, GE_POL_EVALUATE = 2, GE_POL_MODES = 3, GE_POL_GRAD = 3 };
 #define GE_POL_THREADS 256
 #define GE_POL_REG_CHUNKS 32  // chunks of a row held in registers: 64 * 32 = 2 048 actions
 #define GE_POL_BLOCK 8        // chunks a longer row loads back to back
@@ -29,12 +37,14 @@ template <int N> struct GeInt { static constexpr int value = N; };
 
 struct GePolicyIO {
   const float *logits;    // the classes' [B_c, A_c] blocks one after the other (GeParams.policy_off)
-  const uint8_t *mask;    // evaluate: bool bytes in the layout of logits
-  const int64_t *given;   // evaluate: the actions to score
+  const uint8_t *mask;    // evaluate, gradient: bool bytes in the layout of logits
+  const int64_t *given;   // evaluate, gradient: the actions to score
   int64_t *actions;       // sample, greedy
   float *logp, *entropy;  // may be NULL
   uint64_t policy_seed;
   int32_t group;          // lanes per row (GePlan.pol_group)
+  const float *grad_logp, *grad_entropy;  // gradient: upstream [B] of logp and entropy, NULL: zeros
+  float *grad_logits;                     // gradient: out, in the layout of logits
 };
 
 // lane group of a row: lanes [lane - g, lane - g + G), G a power of two.  Every lane of the group executes these.
@@ -66,7 +76,7 @@ template <int MODE>
 GE_DEV void ge_pol_chunk(float xj, bool v, int first, float mx, float t, int lane, int G, float &s1, float &carry, int &act) {
   const float d = v ? xj - mx : 0.0f, w = v ? expf(d) : 0.0f;
   s1 += w * d;
-  if (MODE == GE_POL_EVALUATE || act >= 0) return;  // (act is the same in every lane of the group)
+  if (MODE == GE_POL_EVALUATE || MODE == GE_POL_GRAD || act >= 0) return;  // (act is the same in every lane of the group)
   if (MODE == GE_POL_GREEDY) {
     const uint64_t hit = ge_grp_ballot(v && xj == mx, lane, G);
     if (hit) act = first + ge_ctz64(hit);
@@ -78,8 +88,25 @@ GE_DEV void ge_pol_chunk(float xj, bool v, int first, float mx, float t, int lan
   else carry = ge_shfl_f32(p, (lane | (G - 1)));
 }
 
+// the row's entropy from its gathered s1 and Z; lz = logf(Z).  Every lane of the group executes this.
+GE_DEV float ge_pol_entropy(float s1, float Z, int lane, int G, float &lz) {
+  const float S1 = ge_grp_sum(s1, lane, G);
+  lz = logf(Z);
+  return lz - S1 / Z;
+}
+
+// what the gradient of a row's elements shares: a row without a valid action keeps the zeros (none of its elements is valid)
+struct GePolGradRow { float mx, lz, rZ, H, gl, gh; int astar; };
+GE_DEV float ge_pol_grad_at(const GePolGradRow &c, float xj, bool v, int idx) {
+  const float d = v ? xj - c.mx : 0.0f, p = expf(d) * c.rZ, lp = d - c.lz;
+  const float gr = c.gl * ((idx == c.astar ? 1.0f : 0.0f) - p) - c.gh * (p * (lp + c.H));
+  return v ? gr : 0.0f;
+}
+
+// The body of ge_k_policy_head<RAGGED, MODE> and, with MODE = GE_POL_GRAD, of ge_k_policy_grad<RAGGED>.
 template <bool RAGGED, int MODE>
-GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePolicyIO io) {
+GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO &io) {
+  constexpr bool EVAL = MODE == GE_POL_EVALUATE || MODE == GE_POL_GRAD;  // validity from the caller's bytes, nothing of the episode read
   const int tid = ge_tid(), lane = tid & 63;
   const int G = io.group, g = lane & (G - 1), gbase = lane - g;
   const int64_t item = (int64_t)ge_bid() * (GE_POL_THREADS / 64) + (tid >> 6);  // this wave's 64 / G rows
@@ -96,14 +123,14 @@ GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePoli
   const int i = ig - lo, A = P.A, AW = P.AW;
   const int64_t row = P.policy_off + (int64_t)i * A;
   const float *x = io.logits + row;
-  const uint8_t *mbytes = MODE == GE_POL_EVALUATE ? io.mask + row : nullptr;
+  const uint8_t *mbytes = EVAL ? io.mask + row : nullptr;
   const uint64_t *mb = P.buf.mask_bits + (int64_t)i * AW;
   const int nch = G < 64 ? 1 : (A + 63) >> 6;  // (G < 64: every row of the launch fits its group)
   // mask words j0 .. j0 + G - 1 of the row, word j0 + g in lane g: one unconditional load (a word past the end re-reads word 0)
   auto words_at = [&](int j0) { return mb[j0 + g < AW ? j0 + g : 0]; };
   const bool writer = g == 0;
   uint64_t packed = 0;
-  if (MODE != GE_POL_EVALUATE) packed = P.buf.slot_rec[2 * (int64_t)i + 1];
+  if (!EVAL) packed = P.buf.slot_rec[2 * (int64_t)i + 1];
 
   float mx = -INFINITY, Z = 0.0f, s1 = 0.0f, carry = 0.0f, t = 0.0f;
   int act = -1, last = -1;  // last: the highest valid action of this lane
@@ -112,7 +139,22 @@ GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePoli
     const uint64_t z = ge_mix64(io.policy_seed + (uint64_t)(P.env_index_base + i) * 0x9E3779B97F4A7C15ull + ge_rec_tstep(packed) * 0xD1B54A32D192ED03ull);
     return ((float)(z >> 40) * 0x1p-24f) * Z;
   };
-  const bool frozen = MODE != GE_POL_EVALUATE && ge_policy_idle(1u, ge_rec_status(packed));
+  const bool frozen = !EVAL && ge_policy_idle(1u, ge_rec_status(packed));
+  // gradient: the row's action and upstream gradients, asked for in front of the row (every lane of the group: one address each)
+  GePolGradRow gr = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, -1};
+  if (MODE == GE_POL_GRAD) {
+    const int64_t a = io.given[ig];
+    const bool ok = a >= 0 && a < (int64_t)A && mbytes[a] != 0;  // else the forward's logp is -inf: its gradient is dropped
+    if (ok) gr.astar = (int)a;
+    if (ok && io.grad_logp) gr.gl = io.grad_logp[ig];
+    if (io.grad_entropy) gr.gh = io.grad_entropy[ig];
+  }
+  float *gout = MODE == GE_POL_GRAD ? io.grad_logits + row : nullptr;
+  auto grad_row = [&]() {  // after the row pass (any, mx, Z, s1)
+    if (!any) return;
+    gr.mx = mx; gr.rZ = 1.0f / Z;
+    gr.H = ge_pol_entropy(s1, Z, lane, G, gr.lz);
+  };
   // ---- the row in registers.  NCH, the row's chunk count rounded up to a power of two, is a compile-time constant: the loops
   // unroll fully, xv[] is indexed statically and the NCH loads (a chunk past the row re-reads element 0) are issued back to back
   // in front of the first use.
@@ -122,36 +164,57 @@ GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePoli
     uint8_t mv[NCH];
     uint32_t vb = 0;  // bit j: element j * G + g is a valid action
     uint64_t words = 0;
-    if (MODE != GE_POL_EVALUATE) words = words_at(0);
+    if (!EVAL) words = words_at(0);
 #pragma unroll
     for (int j = 0; j < NCH; j++) {
       const int idx = j * G + g;
       xv[j] = x[idx < A ? idx : 0];
-      if (MODE == GE_POL_EVALUATE) mv[j] = mbytes[idx < A ? idx : 0];
+      if (EVAL) mv[j] = mbytes[idx < A ? idx : 0];
     }
     float m = -INFINITY;
 #pragma unroll
     for (int j = 0; j < NCH; j++) {
       const int idx = j * G + g;
       bool v;  // (every lane of the group takes part in the shuffle, also one past the row's end)
-      if (MODE == GE_POL_EVALUATE) v = idx < A && mv[j] != 0;
+      if (EVAL) v = idx < A && mv[j] != 0;
       else { const uint64_t mw = ge_shfl_u64(words, gbase + j); v = idx < A && ((mw >> (idx & 63)) & 1ull) != 0ull; }
       vb |= (uint32_t)v << j;
       if (v) m = fmaxf(m, xv[j]);
     }
     mx = ge_grp_max(m, lane, G);
     any = ge_grp_ballot(vb != 0u, lane, G) != 0ull;
-    if (!any || frozen) return;
-    float s = 0.0f;
+    if (any && !frozen) {
+      float s = 0.0f;
 #pragma unroll
-    for (int j = 0; j < NCH; j++)
-      if ((vb >> j) & 1u) s += expf(xv[j] - mx);
-    Z = ge_grp_sum(s, lane, G);
-    if (MODE == GE_POL_SAMPLE) t = threshold();
+      for (int j = 0; j < NCH; j++)
+        if ((vb >> j) & 1u) s += expf(xv[j] - mx);
+      Z = ge_grp_sum(s, lane, G);
+      if (MODE == GE_POL_SAMPLE) t = threshold();
 #pragma unroll
-    for (int j = 0; j < NCH; j++)
-      if (j < nch) ge_pol_chunk<MODE>(xv[j], ((vb >> j) & 1u) != 0u, j * G, mx, t, lane, G, s1, carry, act);
-    if (vb) last = (31 - ge_clz32(vb)) * G + g;
+      for (int j = 0; j < NCH; j++)
+        if (j < nch) ge_pol_chunk<MODE>(xv[j], ((vb >> j) & 1u) != 0u, j * G, mx, t, lane, G, s1, carry, act);
+      if (vb) last = (31 - ge_clz32(vb)) * G + g;
+    }
+    if (MODE == GE_POL_GRAD) {  // the gradient from the registers: NCH values, then their stores back to back
+      grad_row();
+      float gv[NCH];
+#pragma unroll
+      for (int j = 0; j < NCH; j++) gv[j] = ge_pol_grad_at(gr, xv[j], ((vb >> j) & 1u) != 0u, j * G + g);
+      // a row of more than NCH / 2 chunks of 64 lanes (every row the dispatch below hands an NCH >= 2) holds its first NCH / 2 chunks
+      // whole: every lane stores them, without a test
+      constexpr int HALF = NCH / 2;
+      if (G == 64 && nch > HALF) {
+#pragma unroll
+        for (int j = 0; j < HALF; j++) gout[j * 64 + g] = gv[j];
+#pragma unroll
+        for (int j = HALF; j < NCH; j++)
+          if (j * 64 + g < A) gout[j * 64 + g] = gv[j];
+      } else {
+#pragma unroll
+        for (int j = 0; j < NCH; j++)
+          if (j * G + g < A) gout[j * G + g] = gv[j];
+      }
+    }
   };
   if (nch <= 1) in_regs(GeInt<1>());
   else if (nch <= 2) in_regs(GeInt<2>());
@@ -167,17 +230,17 @@ GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePoli
     float xs[GE_POL_BLOCK];
     uint8_t ms[GE_POL_BLOCK];
     auto load_block = [&](int j0) {  // (a chunk past the row re-reads element 0 and counts as invalid)
-      if (MODE != GE_POL_EVALUATE && (j0 & 63) == 0) words = words_at(j0);
+      if (!EVAL && (j0 & 63) == 0) words = words_at(j0);
 #pragma unroll
       for (int k = 0; k < GE_POL_BLOCK; k++) {
         const int idx = (j0 + k) * 64 + lane;
         xs[k] = x[idx < A ? idx : 0];
-        if (MODE == GE_POL_EVALUATE) ms[k] = mbytes[idx < A ? idx : 0];
+        if (EVAL) ms[k] = mbytes[idx < A ? idx : 0];
       }
     };
     auto valid_at = [&](int j0, int k) {
       const int idx = (j0 + k) * 64 + lane;
-      if (MODE == GE_POL_EVALUATE) return idx < A && ms[k] != 0;
+      if (EVAL) return idx < A && ms[k] != 0;
       const uint64_t mw = ge_shfl_u64(words, (j0 + k) & 63);  // (every lane takes part, also one past the row's end)
       return idx < A && ((mw >> (idx & 63)) & 1ull) != 0ull;
     };
@@ -205,12 +268,25 @@ GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePoli
           if (j0 + k < nch) ge_pol_chunk<MODE>(xs[k], valid_at(j0, k), (j0 + k) * 64, mx, t, lane, G, s1, carry, act);
       }
     }
+    if (MODE == GE_POL_GRAD) {  // a third read of the row
+      grad_row();
+      for (int j0 = 0; j0 < nch; j0 += GE_POL_BLOCK) {
+        load_block(j0);
+        float gv[GE_POL_BLOCK];
+#pragma unroll
+        for (int k = 0; k < GE_POL_BLOCK; k++) gv[k] = ge_pol_grad_at(gr, xs[k], valid_at(j0, k), (j0 + k) * 64 + lane);
+#pragma unroll
+        for (int k = 0; k < GE_POL_BLOCK; k++)
+          if ((j0 + k) * 64 + lane < A) gout[(j0 + k) * 64 + lane] = gv[k];
+      }
+    }
   }
+  if (MODE == GE_POL_GRAD) return;
   const bool idle = !any || frozen;
   float lp = 0.0f, ent = 0.0f;
   if (!idle) {
-    const float S1 = ge_grp_sum(s1, lane, G), lz = logf(Z);
-    ent = lz - S1 / Z;
+    float lz;
+    ent = ge_pol_entropy(s1, Z, lane, G, lz);
     // rounding left no prefix above t: the last valid action (greedy: only non-finite logits get here; x[act] stays inside the row)
     if (MODE != GE_POL_EVALUATE && act < 0) act = ge_grp_max_i32(last, lane, G);
   }
@@ -226,3 +302,9 @@ GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePoli
   if (io.logp) io.logp[ig] = lp;
   if (io.entropy) io.entropy[ig] = ent;
 }
+
+template <bool RAGGED, int MODE>
+GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePolicyIO io) { ge_pol_rows<RAGGED, MODE>(PG, R, io); }
+
+template <bool RAGGED>
+GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_grad(GeParams PG, GeRagged R, GePolicyIO io) { ge_pol_rows<RAGGED, GE_POL_GRAD>(PG, R, io); }

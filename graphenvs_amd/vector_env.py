@@ -182,6 +182,35 @@ def slot_seeds(seed, num_envs, env_index_base, device):
     return torch.from_numpy(s.astype(np.uint32).view(np.int32)).to(device)
 
 
+class _EvaluateActions(torch.autograd.Function):
+    """evaluate_actions with a gradient for the logits: ge_policy_evaluate forward, ge_policy_backward backward (one launch each).
+    The outputs are fresh tensors -- a training step holds several evaluations alive; save_for_backward makes an in-place change of
+    the logits, mask or actions before backward() torch's own error."""
+
+    @staticmethod
+    def forward(ctx, x, actions, mask, env):
+        logp, entropy = (torch.empty(env.num_envs, dtype=torch.float32, device=env.device) for _ in range(2))
+        env._call("ge_policy_evaluate", x.data_ptr(), mask.data_ptr(), actions.data_ptr(), logp.data_ptr(), entropy.data_ptr(), env._stream())
+        ctx.env = env
+        ctx.set_materialize_grads(False)  # (an output the loss does not use reaches backward as None, not as a tensor of zeros)
+        ctx.save_for_backward(x, mask, actions)
+        return logp, entropy
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_logp, grad_entropy):
+        env = ctx.env
+        if not env._h:
+            raise RuntimeError("graphenvs_amd: backward through evaluate_actions() of a closed engine")
+        x, mask, actions = ctx.saved_tensors
+        # (an upstream gradient is often an expanded stride-0 view -- the one of a .mean() loss -- or absent: NULL stands for zeros)
+        up = [None if g is None else g.to(device=env.device, dtype=torch.float32).contiguous() for g in (grad_logp, grad_entropy)]
+        grad = torch.empty_like(x)  # (x is contiguous; the launch writes every element.  The locals outlive the enqueue below)
+        env._call("ge_policy_backward", x.data_ptr(), mask.data_ptr(), actions.data_ptr(), *(None if g is None else g.data_ptr() for g in up),
+                  grad.data_ptr(), env._stream())
+        return grad, None, None, None
+
+
 class EngineHandle:
     """What owns a ge_* handle: ``_L`` the library, ``_h`` the handle, ``device``, and the calls that are the same for a uniform
     and a multi-class engine.  A subclass sets those three, ``num_envs`` and ``_actions_scratch`` (int64, one entry per slot), and
@@ -268,13 +297,20 @@ class EngineHandle:
         uint8, one element per logit -- what info['mask'] (``mask_flat``) held when the actions were drawn, cloned into the rollout
         buffer; the engine's live mask is not read.  On the logits, mask and actions of a sample_actions() call it returns that
         call's logp and entropy bit for bit.  An action of -1, out of range or masked out gives -inf.  The two tensors are
-        allocated once per engine and overwritten by the next evaluate_actions()."""
+        allocated once per engine and overwritten by the next evaluate_actions().
+
+        Differentiable in the logits: when ``logits.requires_grad`` and grad mode is on, the same values come back in fresh tensors
+        with a ``grad_fn`` whose backward is one launch (ge_policy_backward, DESIGN.md 5: masked logits get a gradient of exactly
+        0.0, a row whose action scored -inf drops its logp gradient, first order only).  sample_actions() and step_policy() carry no
+        gradient: an on-policy update calls evaluate_actions() with the cloned mask and the drawn actions."""
         x = self._policy_input(logits, "logits", (torch.float32,))
         mk = self._policy_input(mask, "mask", (torch.bool, torch.uint8)).view(torch.uint8)
         if not torch.is_tensor(actions):
             actions = torch.as_tensor(np.asarray(actions, dtype=np.int64))
         a = actions.to(device=self.device, dtype=torch.int64).contiguous()
         assert a.shape == (self.num_envs,)
+        if x.requires_grad and torch.is_grad_enabled():
+            return _EvaluateActions.apply(x, a, mk, self)
         o = self._policy_buffers()
         self._evaluate_keepalive = (x, mk, a)
         self._call("ge_policy_evaluate", x.data_ptr(), mk.data_ptr(), a.data_ptr(), o["eval_logp"].data_ptr(), o["eval_entropy"].data_ptr(),

@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define GE_ABI_VERSION 6
+#define GE_ABI_VERSION 7
 
 /* env ids of graph_envs/__init__.py:9-56 that are on the hot path */
 enum {
@@ -299,6 +299,20 @@ int ge_policy_sample(ge_engine *e, const float *logits, uint64_t policy_seed, in
  * of -1, outside [0, A) or with a zero mask byte gives logp = -inf; the entropy is the row's, 0 for an all-zero row. */
 int ge_policy_evaluate(ge_engine *e, const float *logits, const uint8_t *mask, const int64_t *actions,
                        float *logp, float *entropy, void *stream);
+
+/* The gradient of ge_policy_evaluate's outputs with respect to the logits, in one launch of the forward's geometry: the backward of a
+ * PPO / A2C loss built from logp and entropy.  logits, mask and actions as in ge_policy_evaluate (same layout; no episode is needed).
+ * grad_logp, grad_entropy: the upstream gradients gl, gh of the two outputs, [B] float32; either may be NULL, meaning zeros.
+ * grad_logits (required, the layout of logits; it may arrive uninitialised): with p = w / Z, lp = d - logf(Z) and H the row's entropy,
+ *    grad[a] = gl ([a == action] - p[a]) - gh p[a] (lp[a] + H)   for a valid a,     grad[a] = 0.0   for a masked a.
+ *  - every element of every row is written; an all-zero mask row gets zeros, a row with one valid action too (p = 1, lp = H = 0);
+ *  - a row whose action is -1, outside [0, A) or masked out (logp = -inf in the forward) drops its gl term whatever gl holds; the gh
+ *    term still flows;
+ *  - mx, Z and the entropy come from the forward's own row pass, and a row's gradient depends on the row alone: shards and ranks
+ *    reproduce the unsharded gradient bit for bit.  Non-finite logits or upstream gradients are the caller's contract (no defined
+ *    value; every access stays in bounds).  First order only: nothing differentiates the gradient again. */
+int ge_policy_backward(ge_engine *e, const float *logits, const uint8_t *mask, const int64_t *actions,
+                       const float *grad_logp, const float *grad_entropy, float *grad_logits, void *stream);
 
 /* ge_policy_sample followed by ge_step(actions) on `stream`, without the host in between: one call per step of a training rollout.
  * Same call-order guard as ge_step. */
