@@ -102,7 +102,13 @@ GE_DEV int ge_clz32(uint32_t v) { return v ? (int)__builtin_clz(v) : 32; }
 // dependent round trips outranks the feature kernels, which are the throughput tenants and fill the issue slots the others leave.
 // Only the assignments that were measured beside other engines carry a level: the n <= 64 step kernel and the probe of the generic
 // feature kernel's LIST launch.  ge_k_step, ge_k_step_edge, ge_k_swap and ge_k_feat_combine stay at 0 until the configs that launch
-// them are measured.  The graph kernel stays at 0 (its retrying waves at 1): raised as a whole it gains nothing, and raised above
-// its own seeding workgroups it starves them and the launch ends later (profiles/README.md round 5).
+// them are measured.  The graph kernel's regenerating waves stay at 0 (retrying ones at 1): raised as a whole it gains nothing, and
+// raised above its own seeding workgroups it starves them and the launch ends later (profiles/README.md round 5);
+// the seeding workgroups ALONE are raised (round 8).
+#ifndef GE_PRIO_SEED
+#define GE_PRIO_SEED 1   // the seeding workgroups of the queue-mode graph launch (ge_k_reset): two waves per 64 queued slots running a chain of
+                         // 1 869 dependent steps, the LAST waves of the launch to finish (without them the launch is 57 us instead of 74 beside
+                         // two other shards, profiles/README.md round 8) -- a handful of waves on the whole chip, so raising them costs nobody
+#endif
 #define GE_PRIO_STEP 3   // ge_k_step_path64: every wave, from entry to exit
 #define GE_PRIO_PROBE 3  // a LIST-mode launch of ge_k_features until it has read work_count; with work to do it drops to 0

@@ -2128,6 +2128,7 @@ GE_KERNEL_LB(GE_RESET_THREADS, GE_RESET_WAVES_PER_SIMD) ge_k_reset(GeParams P, G
     count = pre[nblk];
   }
   if (queue && ge_bid() < nseed) {
+    ge_wave_priority(GE_PRIO_SEED);  // the launch ends with these waves (ge_platform.h)
     for (int g0 = ge_bid() * GE_WAVE; g0 < count; g0 += nseed * GE_WAVE) {
       const int tid = ge_tid_fresh();
       if (g0 != ge_bid() * GE_WAVE) { if (tid < GE_WAVE) ge_queue_prefix_wave(P, pre, tid); ge_sync(); }
