@@ -35,6 +35,8 @@ struct GePlan {
   int n_buckets;  // 1: uniform engine
   GeBucket bk[GE_MAX_BUCKETS];
   int nseed;      // seeding workgroups at the head of the queue-mode reset launch (64 queued slots each)
+  int nseed2;     // split seeding (GE_SEED_SPLIT; a uniform engine on the n <= 64 fast path, until spares are attached): pass-2 workgroups
+                  // at the head of ge_k_features64's queue launch, GE_SEED2_ITEMS queued slots each; 0: the graph launch seeds to the end
   bool feat_fast;                       // a class takes the n <= 64 feature kernel (spatial TSP: float64 weights do not fit its LDS)
   int f64_lds, f64_pre_off, feat_grid;  // that kernel's launch; feat_grid without it: resident workgroups of the generic kernel at the largest class's carve
   GeLds inject;   // ge_inject_state runs the graph kernel on this carve (inject_carve)
@@ -99,7 +101,7 @@ static GeRun run_continue() { GeRun r = {GE_ITEMS_ALL, 0, 1, 1, 0, 0, 0}; return
 // finished slots regenerated in place.  Without spares the launch that moves a slot to episode e + 1 refills ring entry e with
 // episode e + GE_SEED_DEPTH; with spares every regeneration of a slot -- refill or in place -- seeds the episode after the one it
 // generates, two past the one seed[] / episode[] name
-static GeRun run_queue(const ge_engine *e) { GeRun r = {GE_ITEMS_QUEUE, 0, 1, 0, 0, 0, e->spares ? 2 : GE_SEED_DEPTH}; return r; }
+static GeRun run_queue(const ge_engine *e) { GeRun r = {GE_ITEMS_QUEUE, 0, 1, 0, 0, 0, e->spares ? 2 : GE_SEED_DEPTH, e->plan.nseed2}; return r; }
 static GeRun run_refill() { GeRun r = {GE_ITEMS_QUEUE, 0, 1, 0, 0, 1, 2}; return r; }
 static GeRun as_list(GeRun r) { r.items = GE_ITEMS_LIST; return r; }  // the feature kernels' fallback list of the same launch sequence
 
@@ -397,6 +399,11 @@ static int finish_create(ge_engine *e) {
   // ---- n <= 64 feature kernel: the item bodies (the queue prefix overlays them), then the tail {item slots, overflow flag}
   L.f64_pre_off = ge_align16(f64_body);
   L.f64_lds = L.feat_fast ? L.f64_pre_off + GE_F64_ITEMS * 4 * 4 + 16 : 0;
+  // ---- split seeding: as many pass-2 workgroups as cover the slots of the graph launch's seeding workgroups in one trip; a
+  // pass-2 workgroup's tiles lie inside the feature launch's carve (the headline's is larger: nothing changes there)
+  L.nseed2 = (GE_SEED_SPLIT && !rg && L.feat_fast) ? (L.nseed * GE_WAVE + GE_SEED2_ITEMS - 1) / GE_SEED2_ITEMS : 0;
+  const int seed2_lds = GE_SEED2_WAVES * GE_SEED2_WAVE_BYTES;
+  if (L.nseed2 > 0 && L.f64_lds < seed2_lds) L.f64_lds = seed2_lds;
   if (!carves_fit({L.f64_lds})) return fail(GE_E_TOOBIG, "feature kernel does not fit LDS");
   if (!raise_lds((const void *)e->k.features, gen_lds)) return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the feature kernel");
   if (L.feat_fast && !raise_lds((const void *)e->k.features64, L.f64_lds)) return fail(GE_E_LAUNCH, "cannot raise the dynamic LDS limit of the n<=64 feature kernel");
@@ -570,6 +577,7 @@ extern "C" int ge_attach_spares(ge_engine *e, const ge_spares *sp, void *class_t
   if (parts >= 4) parts = GE_SWAP_GROUPS;  // a large image: one workgroup per (group of) whole arrays
   e->swap_parts = parts;
   e->spares = true;
+  e->plan.nseed2 = 0;  // an engine with spares seeds two episodes ahead from refill and in-place launches alike: unsplit
   // (the caller zeroes `state`; ge_reset / ge_inject_state clear it and refill every image)
   return GE_OK;
 }
@@ -638,7 +646,13 @@ static int launch_features(ge_engine *e, const GeParams &V, const GeRagged &VR, 
   const GeRun rest = L.feat_fast ? as_list(run) : run;  // behind the fast path: its fallback list
   int rc = GE_OK;
   if (L.feat_fast) {
-    GE_LAUNCH(e->k.features64, fast_grid(e, V.B, run.items == GE_ITEMS_QUEUE, small), GE_F64_THREADS, L.f64_lds, stream, V, VR, run, L.f64_pre_off);
+    // split seeding: the pass-2 workgroups come out of the launch's resident grid, not on top of it -- a workgroup beyond the
+    // resident round starts when another ends, i.e. runs its items as a tail behind the launch (one engine: 123 -> 141 us)
+    const bool queue = run.items == GE_ITEMS_QUEUE;
+    const int nseed2 = queue ? run.seed_split : 0;
+    int grid = fast_grid(e, V.B, queue, small) - nseed2;
+    if (grid < 1) grid = 1;
+    GE_LAUNCH(e->k.features64, grid + nseed2, GE_F64_THREADS, L.f64_lds, stream, V, VR, run, L.f64_pre_off);
     rc = check_launch("feature kernel (n <= 64)");
   }
   for (int b = 0; b < L.n_buckets && rc == GE_OK; b++) {  // one launch per LDS bucket

@@ -814,6 +814,33 @@ GE_F64_KERNEL ge_k_features64(GeParams P, GeRagged R, GeRun run, int tail_off) {
   int *const items = (int *)(ge_dyn_smem() + tail_off);  // [GE_F64_ITEMS][4] slots (walk item: the first; -1 = none)
   int *const ovf_flag = items + GE_F64_ITEMS * 4;
   const bool queue = run.items == GE_ITEMS_QUEUE;
+  // split seeding (GeRun.seed_split): the first nseed2 workgroups finish the ring entries whose python state the graph launch left
+  // behind pass 1 -- a wave per 64 queued slots, nothing here waits for them -- and are the ONE writer of seed[] / episode[] of
+  // the queued slots: a lane reads both to find its item's ring entry, then advances them itself (workgroups of a launch are not
+  // ordered: a walk item that advanced its slot could do so before or after that read).  Walk and node items shift by nseed2.
+  const int nseed2 = (GE_SEED_SPLIT && queue) ? run.seed_split : 0;
+  if (nseed2 > 0 && ge_bid() < nseed2) {
+    ge_wave_priority(GE_PRIO_SEED2);
+    for (int g0 = ge_bid() * GE_SEED2_ITEMS;; g0 += nseed2 * GE_SEED2_ITEMS) {
+      const int tid = ge_tid_fresh();
+      if (tid < GE_WAVE) ge_queue_prefix_wave(P, pre, tid);
+      ge_sync();
+      const int count = pre[nblk];
+      if (g0 >= count) break;  // (uniform)
+      const int q = g0 + tid;
+      uint32_t sb = 0xffffffffu;
+      if (tid < GE_SEED2_ITEMS && q < count) {
+        const int env = ge_queue_slot(P, pre, q);
+        sb = (uint32_t)env * GE_SEED_DEPTH + (uint32_t)((P.buf.episode[env] + run.seed_ahead) % GE_SEED_DEPTH);
+        ge_advance_episode(P, env);
+      }
+      ge_sync();  // every lane has its item before the scratch (which holds the queue prefix) is reused
+      if (tid < GE_SEED2_ITEMS) ge_seed_pass2_group(P, ge_dyn_smem(), sb, tid);  // (uniform per wave)
+      ge_sync();
+    }
+    return;
+  }
+  const int bid = ge_bid() - nseed2, gdim = ge_gdim() - nseed2;
   int count = P.B;
   for (int base = 0;; base += GE_F64_ITEMS) {
     const int tid = ge_tid_fresh();
@@ -823,9 +850,9 @@ GE_F64_KERNEL ge_k_features64(GeParams P, GeRagged R, GeRun run, int tail_off) {
       count = pre[nblk];
     }
     const int total = count + (count + 3) / 4;
-    if (ge_bid() + (int64_t)base * ge_gdim() >= total) break;  // (uniform)
+    if (bid + (int64_t)base * gdim >= total) break;  // (uniform)
     if (tid < GE_F64_ITEMS * 4) {
-      const int64_t q = ge_bid() + (int64_t)(base + (tid >> 2)) * ge_gdim();
+      const int64_t q = bid + (int64_t)(base + (tid >> 2)) * gdim;
       const int sub = tid & 3;
       int qi = -1;
       if (q < count) qi = sub == 0 ? (int)q : -1;
@@ -834,11 +861,11 @@ GE_F64_KERNEL ge_k_features64(GeParams P, GeRagged R, GeRun run, int tail_off) {
     }
     ge_sync();
     for (int i = 0; i < GE_F64_ITEMS; i++) {
-      const int64_t q = ge_bid() + (int64_t)(base + i) * ge_gdim();
+      const int64_t q = bid + (int64_t)(base + i) * gdim;
       if (q >= total) break;  // (uniform)
       if (q < count) {  // walk item
         const int env = items[4 * i];
-        if (queue && ge_tid() == 0) ge_finish_item(P, run, env);  // seed[] / episode[] now name the new episode (refill: the image is valid)
+        if (queue && nseed2 == 0 && ge_tid() == 0) ge_finish_item(P, run, env);  // seed[] / episode[] now name the new episode (refill: the image is valid)
         if constexpr (RAGGED) {
           const int cls = ge_slot_class(R, env);
           const GeParams &C = R.classes[cls];

@@ -16,6 +16,14 @@
 #define GE_RESET_THREADS 128
 #define GE_SEED_TILE_STRIDE 68  // u32 per row of a seeding tile [16 words][64 slots]: 68 mod 64 = 4, the flush reads 64 different banks
 #define GE_SEED_LDS_BYTES (2 * 16 * GE_SEED_TILE_STRIDE * 4 + 64 * 4 + 64)
+#ifndef GE_SEED_SPLIT
+#define GE_SEED_SPLIT 1  // a uniform n <= 64 engine without spares runs random.seed's second pass at the head of the feature launch (0: never)
+#endif
+#define GE_SEED2_WAVE_BYTES (16 * GE_SEED_TILE_STRIDE * 4 + 64 * 4)  // a pass-2 wave: its tile and the ring entries of its 64 items
+#ifndef GE_SEED2_WAVES
+#define GE_SEED2_WAVES 4  // waves of a pass-2 workgroup (256 threads) that seed, 64 queued slots each; the others leave it to them
+#endif
+#define GE_SEED2_ITEMS (GE_SEED2_WAVES * 64)
 #ifndef GE_RESET_WAVES_PER_SIMD
 #define GE_RESET_WAVES_PER_SIMD 6  // 24 waves / CU = 12 two-wave workgroups: one round for the ~2 700 resets of a headline step
 #endif
@@ -107,6 +115,9 @@ struct GeRun {
                        // no final_heur, the slot's step count is not read; the feature kernel marks the image valid instead
   int32_t seed_ahead;  // queue launches: seeding workgroups write the states of episode (e + seed_ahead), seeded seed[] + seed_ahead *
                        // seed_stride, into ring entry (e + seed_ahead) % GE_SEED_DEPTH, e = episode[] of the item; 0 = none
+  int32_t seed_split;  // queue launches of an engine whose plan splits the seeding (GePlan.nseed2): the graph launch's python wave
+                       // stops behind pass 1, and the first seed_split workgroups of ge_k_features64 run pass 2 and advance
+                       // seed[] / episode[] of the queued slots (the walk items do not); 0 = the graph launch seeds to the end
 };
 
 // Multi-class ("ragged") engine, BASELINE config 5: slots of different (n, m) stepped by ONE launch sequence.  A size class is a

@@ -110,5 +110,8 @@ GE_DEV int ge_clz32(uint32_t v) { return v ? (int)__builtin_clz(v) : 32; }
                          // 1 869 dependent steps, the LAST waves of the launch to finish (without them the launch is 57 us instead of 74 beside
                          // two other shards, profiles/README.md round 8) -- a handful of waves on the whole chip, so raising them costs nobody
 #endif
+#ifndef GE_PRIO_SEED2
+#define GE_PRIO_SEED2 GE_PRIO_SEED  // the pass-2 workgroups at the head of ge_k_features64's queue launch (split seeding, GE_SEED_SPLIT)
+#endif
 #define GE_PRIO_STEP 3   // ge_k_step_path64: every wave, from entry to exit
 #define GE_PRIO_PROBE 3  // a LIST-mode launch of ge_k_features until it has read work_count; with work to do it drops to 0

@@ -2013,55 +2013,104 @@ GE_DEV void ge_seed_flush(const GeParams &P, const uint32_t *tile, const GeSeedD
   ge_wave_sync();
 }
 
+// random.seed(int) = init_by_array([seed]) ([py] _randommodule.c) in three pieces, so that a launch can stop between the passes.
+// Pass 1, to its end: of its 623 words only the last one and mt[1] are needed to start pass 2 -- returns m1, the value the 624th
+// iteration (i wrapped) leaves in mt[1]; `first` = the pass-1 value of mt[1].
+GE_DEV uint32_t ge_seed_py_pass1(uint32_t seed, uint32_t &first) {
+  uint32_t prev = 19650218u;
+  first = 0u;
+  for (int i = 1; i < GE_MT_N; i++) {
+    prev = (ge_mt_init.v[i] ^ ((prev ^ (prev >> 30)) * 1664525u)) + seed;  // + key[0] + j, j == 0
+    if (i == 1) first = prev;
+  }
+  return (first ^ ((prev ^ (prev >> 30)) * 1664525u)) + seed;
+}
+// `first` is a closed form of the seed: the first step of pass 1
+GE_DEV uint32_t ge_seed_py_first(uint32_t seed) { return (ge_mt_init.v[1] ^ ((19650218u ^ (19650218u >> 30)) * 1664525u)) + seed; }
+// Pass 2 from (seed, m1): pass 1 again in step with it (its words are consumed once, in order: nothing is stored), 39 tile
+// flushes and the final mt[1].  Collective over the wave; `sb` as in ge_seed_group.
+GE_DEV void ge_seed_py_pass2(const GeParams &P, uint32_t *tile, const GeSeedDst &dst, uint32_t sb, uint32_t seed, uint32_t m1, uint32_t first, int lane) {
+  uint32_t *mine = tile + lane;
+  uint32_t prev = m1, p1 = first;
+  for (int c = 0; c < GE_MT_N / 16; c++) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      const int i = 16 * c + k;
+      uint32_t out;
+      if (i == 0) out = 0x80000000u;   // mt[0]
+      else if (i == 1) out = 0u;       // mt[1] is the last word to be known: patched below
+      else {
+        p1 = (ge_mt_init.v[i] ^ ((p1 ^ (p1 >> 30)) * 1664525u)) + seed;          // pass-1 value of mt[i]
+        prev = (p1 ^ ((prev ^ (prev >> 30)) * 1566083941u)) - (uint32_t)i;       // final mt[i]
+        out = prev;
+      }
+      mine[k * GE_SEED_TILE_STRIDE] = out;
+    }
+    ge_seed_flush(P, tile, dst, c, lane);
+  }
+  if (sb != 0xffffffffu) P.buf.mt_state[((int64_t)sb * 2 + 0) * GE_MT_N + 1] = (m1 ^ ((prev ^ (prev >> 30)) * 1566083941u)) - 1u;
+}
+// np.random.seed(int) = init_genrand(seed) ([np] mt19937.c).  Collective over the wave.
+GE_DEV void ge_seed_np_chain(const GeParams &P, uint32_t *tile, const GeSeedDst &dst, uint32_t seed, int lane) {
+  uint32_t *mine = tile + lane;
+  uint32_t prev = seed;
+  for (int c = 0; c < GE_MT_N / 16; c++) {
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+      const int i = 16 * c + k;
+      if (i > 0) prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
+      mine[k * GE_SEED_TILE_STRIDE] = prev;
+    }
+    ge_seed_flush(P, tile, dst, c, lane);
+  }
+}
+
 // one seeding workgroup (two waves) over 64 (slot, ring entry, seed) items: `sb` = slot * GE_SEED_DEPTH + entry of this lane's
 // item or 0xffffffff.  `lds` = GE_SEED_LDS_BYTES of scratch.  Collective over the workgroup (wave-level syncs only).
-GE_DEV void ge_seed_group(const GeParams &P, unsigned char *lds, uint32_t sb, uint32_t seed, int tid) {
+// `split` (the queue launch of an engine whose plan splits, GeRun.seed_split): the python wave stops behind pass 1 and leaves
+// (seed, m1) in words 0 and 1 of the entry's python state -- the entry is free, nobody reads it before the feature launch of the
+// same reset path, whose pass-2 workgroups (ge_seed_pass2_group) finish it and overwrite both words last.
+GE_DEV void ge_seed_group(const GeParams &P, unsigned char *lds, uint32_t sb, uint32_t seed, int tid, bool split = false) {
   const int lane = tid & (GE_WAVE - 1), wv = tid >> 6;
   uint32_t *tile = (uint32_t *)lds + wv * 16 * GE_SEED_TILE_STRIDE;
   uint32_t *base = (uint32_t *)lds + 2 * 16 * GE_SEED_TILE_STRIDE;  // shared by both waves: same items
   if (wv == 0) base[lane] = sb;
   ge_sync();
-  const GeSeedDst dst = ge_seed_dst(base, wv, lane);
-  uint32_t *mine = tile + lane;
-  if (wv == 0) {  // python: init_by_array([seed]) ([py] _randommodule.c)
-    uint32_t prev = 19650218u, first = 0u;
-    for (int i = 1; i < GE_MT_N; i++) {  // pass 1, to its end: only its last word and mt[1] are needed to start pass 2
-      prev = (ge_mt_init.v[i] ^ ((prev ^ (prev >> 30)) * 1664525u)) + seed;  // + key[0] + j, j == 0
-      if (i == 1) first = prev;
+  if (GE_SEED_SPLIT && split && wv == 0) {
+    uint32_t first;
+    const uint32_t m1 = ge_seed_py_pass1(seed, first);
+    if (sb != 0xffffffffu) {
+      uint32_t *py = P.buf.mt_state + ((int64_t)sb * 2 + 0) * GE_MT_N;
+      py[0] = seed; py[1] = m1;
     }
-    const uint32_t m1 = (first ^ ((prev ^ (prev >> 30)) * 1664525u)) + seed;  // i wrapped: the 624th iteration lands on mt[1]
-    prev = m1;
-    uint32_t p1 = first;  // pass 1 again, in step with pass 2 (its words are consumed once, in order: nothing is stored)
-    for (int c = 0; c < GE_MT_N / 16; c++) {
-#pragma unroll
-      for (int k = 0; k < 16; k++) {
-        const int i = 16 * c + k;
-        uint32_t out;
-        if (i == 0) out = 0x80000000u;   // mt[0]
-        else if (i == 1) out = 0u;       // mt[1] is the last word to be known: patched below
-        else {
-          p1 = (ge_mt_init.v[i] ^ ((p1 ^ (p1 >> 30)) * 1664525u)) + seed;          // pass-1 value of mt[i]
-          prev = (p1 ^ ((prev ^ (prev >> 30)) * 1566083941u)) - (uint32_t)i;       // final mt[i]
-          out = prev;
-        }
-        mine[k * GE_SEED_TILE_STRIDE] = out;
-      }
-      ge_seed_flush(P, tile, dst, c, lane);
-    }
-    if (sb != 0xffffffffu) P.buf.mt_state[((int64_t)sb * 2 + 0) * GE_MT_N + 1] = (m1 ^ ((prev ^ (prev >> 30)) * 1566083941u)) - 1u;
-  } else {        // numpy: init_genrand(seed) ([np] mt19937.c)
-    uint32_t prev = seed;
-    for (int c = 0; c < GE_MT_N / 16; c++) {
-#pragma unroll
-      for (int k = 0; k < 16; k++) {
-        const int i = 16 * c + k;
-        if (i > 0) prev = 1812433253u * (prev ^ (prev >> 30)) + (uint32_t)i;
-        mine[k * GE_SEED_TILE_STRIDE] = prev;
-      }
-      ge_seed_flush(P, tile, dst, c, lane);
+  } else {
+    const GeSeedDst dst = ge_seed_dst(base, wv, lane);
+    if (wv == 0) {
+      uint32_t first;
+      const uint32_t m1 = ge_seed_py_pass1(seed, first);
+      ge_seed_py_pass2(P, tile, dst, sb, seed, m1, first, lane);
+    } else {
+      ge_seed_np_chain(P, tile, dst, seed, lane);
     }
   }
   ge_sync();  // the scratch may be reused
+}
+
+// a pass-2 workgroup of the split (head of ge_k_features64's queue launch): any number of waves, 64 items each, every wave on its
+// own tile and item list (GE_SEED2_WAVE_BYTES of `lds` per wave).  Wave-level syncs only; the caller fences the scratch.
+GE_DEV void ge_seed_pass2_group(const GeParams &P, unsigned char *lds, uint32_t sb, int tid) {
+  const int lane = tid & (GE_WAVE - 1), wv = tid >> 6;
+  uint32_t *tile = (uint32_t *)(lds + wv * GE_SEED2_WAVE_BYTES);
+  uint32_t *base = tile + 16 * GE_SEED_TILE_STRIDE;
+  base[lane] = sb;
+  ge_wave_sync();
+  const GeSeedDst dst = ge_seed_dst(base, 0, lane);
+  uint32_t seed = 0u, m1 = 0u;
+  if (sb != 0xffffffffu) {
+    const uint32_t *py = P.buf.mt_state + ((int64_t)sb * 2 + 0) * GE_MT_N;
+    seed = py[0]; m1 = py[1];  // what the graph launch's pass 1 left (the seed already wrapped modulo 2^32)
+  }
+  ge_seed_py_pass2(P, tile, dst, sb, seed, m1, ge_seed_py_first(seed), lane);
 }
 
 // Full reset / seeded injection: ring entries jlo .. GE_SEED_DEPTH - 1 of every slot, entry j from seeds[slot] + j * seed_stride
@@ -2141,7 +2190,7 @@ GE_KERNEL_LB(GE_RESET_THREADS, GE_RESET_WAVES_PER_SIMD) ge_k_reset(GeParams P, G
         seed = P.buf.seed[env] + (uint32_t)run.seed_ahead * (uint32_t)P.seed_stride;
       }
       ge_sync();  // every lane has its item before the scratch (which holds the queue prefix) is reused
-      ge_seed_group(P, ge_dyn_smem(), sb, seed, tid);
+      ge_seed_group(P, ge_dyn_smem(), sb, seed, tid, run.seed_split > 0);
     }
     return;
   }
