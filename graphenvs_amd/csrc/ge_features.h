@@ -393,6 +393,10 @@ GE_DEV void ge_features_generic_env(const GeParams &P, int env, int part, int np
                       // kernel alone: 1 -> 172 us, 2 -> 151, 3 -> 161, 4 -> 172, 6 -> 197: the kernel is bound by vector issue, and entries
                       // that do not exist cost their instructions)
 #endif
+#ifndef GE_F64_L2POP
+#define GE_F64_L2POP 1  // level 2 of a search takes its path counts as popcounts: every node of level 1 has one path, so sigma(v) =
+                        // |adj(v) & level 1| without a set-bit loop (0: the pull of the other levels; the same bytes either way)
+#endif
 #define GE_F64_THREADS 256
 #define GE_F64_WAVES 4
 #define GE_F64_SB 8                      // sources of a wave's sub-batch: eight lanes each
@@ -571,9 +575,20 @@ GE_DEV void ge_f64_walk_env(const GeParams &P, int env, int *ovf_flag, int32_t *
     // level 1 is the source's neighbours: one path each, no pull (a trip of the loop below for every search otherwise)
     { const int lo = lstrow[1], hi = Dw >= 1 ? (int)lstrow[2] : lo; for (int k = lo + o; k < hi; k += 8) sigrow[ordrow[k]] = 1; }  // (Dw == 0: no search of this wave has a level 1, lstrow[2] was not written)
     const bool deep = ge_ballot(ovf) != 0ull;  // the slot goes to the generic kernel: skip the pulls (their level arrays would overrun)
+#if GE_F64_L2POP
+    // level 2: every neighbour in level 1 brings one path -- a popcount, no set-bit loop, no count read (so beside the writes of level 1)
+    if (Dw >= 2 && !deep && !(GE_F64_ABL & 1)) {
+      const uint64_t l1 = lvl[GE_F64_SB + sl];
+      for (int k = lstrow[2] + o, hi = lstrow[3]; k < hi; k += 8) {
+        const int v = ordrow[k]; const uint32_t acc = (uint32_t)ge_popc64(abits[v] & l1);
+        sigrow[v] = (uint8_t)acc;
+        if (GE_F64_INV < 64 && acc >= (uint32_t)GE_F64_INV) ovf = true;  // (below 64: the table has every reciprocal as shipped)
+      }
+    }
+#endif
     ge_wave_sync();
     // ---- (2) path counts: sigma(v) = sum of sigma(u) over v's neighbours u in the level above
-    for (int d = 2; d <= Dw && !deep && !(GE_F64_ABL & 1); d++) {
+    for (int d = GE_F64_L2POP ? 3 : 2; d <= Dw && !deep && !(GE_F64_ABL & 1); d++) {
       const int lo = lstrow[d], hi = lstrow[d + 1];
       const uint64_t prev = lvl[(d - 1) * GE_F64_SB + sl];
       for (int k = lo + o; ge_ballot(k < hi) != 0ull; k += 8) {
