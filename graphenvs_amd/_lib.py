@@ -98,6 +98,7 @@ SYMBOLS = [
     "ge_reset_pending", "ge_reset_continue", "ge_inject_state", "ge_mark_restored", "ge_vectorize", "ge_sample_actions", "ge_random_rollout",
     "ge_timed_rollout", "ge_timed_step_burst", "ge_timed_empty_burst", "ge_last_error", "ge_source_hash", "ge_attach_spares",
     "ge_policy_sample", "ge_policy_evaluate", "ge_policy_step", "ge_policy_backward",
+    "ge_policy_sample_as", "ge_policy_evaluate_as", "ge_policy_step_as", "ge_policy_backward_as",
 ]
 
 
@@ -198,6 +199,14 @@ def bind(lib):
     lib.ge_policy_evaluate.argtypes = [vp, vp, vp, vp, vp, vp, vp]  # (logits, mask, actions, logp, entropy, stream)
     lib.ge_policy_backward.restype = C.c_int
     lib.ge_policy_backward.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]  # (logits, mask, actions, grad_logp, grad_entropy, grad_logits, stream)
+    f32 = C.c_float
+    for name in ("ge_policy_sample_as", "ge_policy_step_as"):  # (logits, logits_dtype, scale, policy_seed, greedy, actions, logp, entropy, stream)
+        getattr(lib, name).restype = C.c_int
+        getattr(lib, name).argtypes = [vp, vp, i32, f32, u64, i32, vp, vp, vp, vp]
+    lib.ge_policy_evaluate_as.restype = C.c_int
+    lib.ge_policy_evaluate_as.argtypes = [vp, vp, i32, f32, vp, vp, vp, vp, vp]  # (logits, logits_dtype, scale, mask, actions, logp, entropy, stream)
+    lib.ge_policy_backward_as.restype = C.c_int  # (logits, logits_dtype, scale, mask, actions, grad_logp, grad_entropy, grad_logits, stream)
+    lib.ge_policy_backward_as.argtypes = [vp, vp, i32, f32, vp, vp, vp, vp, vp, vp]
     lib.ge_random_rollout.restype = C.c_int
     lib.ge_random_rollout.argtypes = [vp, u64, i32, vp, vp]
     lib.ge_timed_rollout.restype = C.c_int
@@ -218,7 +227,7 @@ def bind(lib):
 _lib = None
 
 
-ABI_VERSION = 7  # GE_ABI_VERSION of include/graphenvs.h this host was written against
+ABI_VERSION = 8  # GE_ABI_VERSION of include/graphenvs.h this host was written against
 
 
 def load():

@@ -55,8 +55,9 @@ struct GeKernels {
   void (*feat_combine)(GeParams, GeRagged, GeRun);
   void (*swap)(GeParams, GeRagged, GeRagged, ge_buffers, int);
   void (*sample)(GeParams, GeRagged, uint64_t, int64_t *);
-  void (*policy_head[GE_POL_MODES])(GeParams, GeRagged, GePolicyIO);  // [GE_POL_SAMPLE / GE_POL_GREEDY / GE_POL_EVALUATE]
-  void (*policy_grad)(GeParams, GeRagged, GePolicyIO);     // the logits gradient of GE_POL_EVALUATE's outputs
+  // [GE_LOGITS_F32 / GE_LOGITS_BF16 / GE_LOGITS_F16: the logits' storage type][GE_POL_SAMPLE / GE_POL_GREEDY / GE_POL_EVALUATE]
+  void (*policy_head[GE_LOGITS_DTYPES][GE_POL_MODES])(GeParams, GeRagged, GePolicyIO);
+  void (*policy_grad[GE_LOGITS_DTYPES])(GeParams, GeRagged, GePolicyIO);  // the logits gradient of GE_POL_EVALUATE's outputs
   void (*dc_range)(GeParams, GeRagged, const int64_t *);
   void (*tsp_closure)(GeParams, GeRagged, int, uint8_t *, uint64_t, int);
   GeBaselineFn tsp_tour, mis_baseline, steiner_baseline;
@@ -293,6 +294,14 @@ static bool path64(const ge_engine *e) {
 
 // The only place where an engine becomes kernel instantiations (e->P, e->n_classes and e->aw_max are final).  `if constexpr` keeps
 // the set of instantiations to the ones an engine can run: the library is one translation unit and every extra kernel costs build time.
+template <bool RAGGED, class T>
+static void select_policy_kernels(GeKernels &k, int dtype) {
+  k.policy_head[dtype][GE_POL_SAMPLE] = ge_k_policy_head<RAGGED, GE_POL_SAMPLE, T>;
+  k.policy_head[dtype][GE_POL_GREEDY] = ge_k_policy_head<RAGGED, GE_POL_GREEDY, T>;
+  k.policy_head[dtype][GE_POL_EVALUATE] = ge_k_policy_head<RAGGED, GE_POL_EVALUATE, T>;
+  k.policy_grad[dtype] = ge_k_policy_grad<RAGGED, T>;
+}
+
 template <int ENV, bool RAGGED>
 static void select_kernels(ge_engine *e) {
   GeKernels &k = e->k;
@@ -302,10 +311,9 @@ static void select_kernels(ge_engine *e) {
   k.feat_combine = ge_k_feat_combine<RAGGED>;
   k.swap = ge_k_swap<RAGGED>;
   k.sample = ge_k_sample<RAGGED>;
-  k.policy_head[GE_POL_SAMPLE] = ge_k_policy_head<RAGGED, GE_POL_SAMPLE>;
-  k.policy_head[GE_POL_GREEDY] = ge_k_policy_head<RAGGED, GE_POL_GREEDY>;
-  k.policy_head[GE_POL_EVALUATE] = ge_k_policy_head<RAGGED, GE_POL_EVALUATE>;
-  k.policy_grad = ge_k_policy_grad<RAGGED>;
+  select_policy_kernels<RAGGED, float>(k, GE_LOGITS_F32);
+  select_policy_kernels<RAGGED, ge_bf16>(k, GE_LOGITS_BF16);
+  select_policy_kernels<RAGGED, ge_f16>(k, GE_LOGITS_F16);
   k.dc_range = ge_k_dc_range<RAGGED>;
   k.tsp_closure = ge_k_tsp_closure<RAGGED>;
   k.tsp_tour = ge_k_tsp_tour<RAGGED>;
@@ -914,40 +922,74 @@ static int launch_policy_kernel(ge_engine *e, void (*kernel)(GeParams, GeRagged,
   GE_LAUNCH(kernel, e->plan.pol_grid, GE_POL_THREADS, 0, stream, e->P, e->R, io);
   return check_launch(what);
 }
-static int launch_policy(ge_engine *e, int mode, GePolicyIO io, void *stream) {  // mode: GE_POL_SAMPLE / GREEDY / EVALUATE
+// the storage type and the scale of a policy call, before anything is launched
+static int check_policy_input(int32_t dtype, float scale) {
+  if (dtype < 0 || dtype >= GE_LOGITS_DTYPES) return fail(GE_E_BADARG, "logits_dtype is none of GE_LOGITS_F32, GE_LOGITS_BF16, GE_LOGITS_F16");
+  if (!(scale > 0.0f) || !(scale <= 3.402823466e38f)) return fail(GE_E_BADARG, "the logits scale must be finite and > 0");
+  return GE_OK;
+}
+static int launch_policy(ge_engine *e, int mode, int32_t dtype, GePolicyIO io, void *stream) {  // mode: GE_POL_SAMPLE / GREEDY / EVALUATE
   static_assert(GE_POL_GRAD >= GE_POL_MODES, "the gradient is no entry of policy_head");
   if (mode < 0 || mode >= GE_POL_MODES) return fail(GE_E_BADARG, "no such policy head mode");
-  return launch_policy_kernel(e, e->k.policy_head[mode], "policy head kernel", io, stream);
+  return launch_policy_kernel(e, e->k.policy_head[dtype][mode], "policy head kernel", io, stream);
 }
 
+extern "C" int ge_policy_sample_as(ge_engine *e, const void *logits, int32_t logits_dtype, float scale, uint64_t policy_seed, int32_t greedy,
+                                   int64_t *actions, float *logp, float *entropy, void *stream) {
+  if (!e || !logits || !actions) return fail(GE_E_BADARG, "null argument");
+  int rc = check_policy_input(logits_dtype, scale);
+  if (rc != GE_OK) return rc;
+  if (!e->loaded) return fail(GE_E_STATE, "the engine holds no episode yet: call ge_reset (or ge_inject_state) first");
+  GePolicyIO io = {};
+  io.logits = logits; io.scale = scale; io.actions = actions; io.logp = logp; io.entropy = entropy; io.policy_seed = policy_seed;
+  return launch_policy(e, greedy ? GE_POL_GREEDY : GE_POL_SAMPLE, logits_dtype, io, stream);
+}
+
+extern "C" int ge_policy_evaluate_as(ge_engine *e, const void *logits, int32_t logits_dtype, float scale, const uint8_t *mask,
+                                     const int64_t *actions, float *logp, float *entropy, void *stream) {
+  if (!e || !logits || !mask || !actions) return fail(GE_E_BADARG, "null argument");
+  int rc = check_policy_input(logits_dtype, scale);
+  if (rc != GE_OK) return rc;
+  GePolicyIO io = {};
+  io.logits = logits; io.scale = scale; io.mask = mask; io.given = actions; io.logp = logp; io.entropy = entropy;
+  return launch_policy(e, GE_POL_EVALUATE, logits_dtype, io, stream);
+}
+
+extern "C" int ge_policy_backward_as(ge_engine *e, const void *logits, int32_t logits_dtype, float scale, const uint8_t *mask,
+                                     const int64_t *actions, const float *grad_logp, const float *grad_entropy, void *grad_logits, void *stream) {
+  if (!e || !logits || !mask || !actions || !grad_logits) return fail(GE_E_BADARG, "null argument");
+  int rc = check_policy_input(logits_dtype, scale);
+  if (rc != GE_OK) return rc;
+  GePolicyIO io = {};
+  io.logits = logits; io.scale = scale; io.mask = mask; io.given = actions;
+  io.grad_logp = grad_logp; io.grad_entropy = grad_entropy; io.grad_logits = grad_logits;
+  return launch_policy_kernel(e, e->k.policy_grad[logits_dtype], "policy gradient kernel", io, stream);
+}
+
+extern "C" int ge_policy_step_as(ge_engine *e, const void *logits, int32_t logits_dtype, float scale, uint64_t policy_seed, int32_t greedy,
+                                 int64_t *actions, float *logp, float *entropy, void *stream) {
+  if (!e || !logits || !actions) return fail(GE_E_BADARG, "null argument");
+  int rc = check_state(e);  // (the guard of ge_step, before anything is launched; the sample call checks logits_dtype and scale)
+  if (rc == GE_OK) rc = ge_policy_sample_as(e, logits, logits_dtype, scale, policy_seed, greedy, actions, logp, entropy, stream);
+  return rc == GE_OK ? ge_step(e, actions, stream) : rc;
+}
+
+// the float32 entry points: the same calls with GE_LOGITS_F32 and scale 1.0f
 extern "C" int ge_policy_sample(ge_engine *e, const float *logits, uint64_t policy_seed, int32_t greedy, int64_t *actions, float *logp,
                                 float *entropy, void *stream) {
-  if (!e || !logits || !actions) return fail(GE_E_BADARG, "null argument");
-  if (!e->loaded) return fail(GE_E_STATE, "the engine holds no episode yet: call ge_reset (or ge_inject_state) first");
-  const GePolicyIO io = {logits, nullptr, nullptr, actions, logp, entropy, policy_seed, 0};
-  return launch_policy(e, greedy ? GE_POL_GREEDY : GE_POL_SAMPLE, io, stream);
+  return ge_policy_sample_as(e, logits, GE_LOGITS_F32, 1.0f, policy_seed, greedy, actions, logp, entropy, stream);
 }
-
 extern "C" int ge_policy_evaluate(ge_engine *e, const float *logits, const uint8_t *mask, const int64_t *actions, float *logp, float *entropy,
                                   void *stream) {
-  if (!e || !logits || !mask || !actions) return fail(GE_E_BADARG, "null argument");
-  const GePolicyIO io = {logits, mask, actions, nullptr, logp, entropy, 0, 0};
-  return launch_policy(e, GE_POL_EVALUATE, io, stream);
+  return ge_policy_evaluate_as(e, logits, GE_LOGITS_F32, 1.0f, mask, actions, logp, entropy, stream);
 }
-
 extern "C" int ge_policy_backward(ge_engine *e, const float *logits, const uint8_t *mask, const int64_t *actions, const float *grad_logp,
                                   const float *grad_entropy, float *grad_logits, void *stream) {
-  if (!e || !logits || !mask || !actions || !grad_logits) return fail(GE_E_BADARG, "null argument");
-  const GePolicyIO io = {logits, mask, actions, nullptr, nullptr, nullptr, 0, 0, grad_logp, grad_entropy, grad_logits};
-  return launch_policy_kernel(e, e->k.policy_grad, "policy gradient kernel", io, stream);
+  return ge_policy_backward_as(e, logits, GE_LOGITS_F32, 1.0f, mask, actions, grad_logp, grad_entropy, grad_logits, stream);
 }
-
 extern "C" int ge_policy_step(ge_engine *e, const float *logits, uint64_t policy_seed, int32_t greedy, int64_t *actions, float *logp,
                               float *entropy, void *stream) {
-  if (!e || !logits || !actions) return fail(GE_E_BADARG, "null argument");
-  int rc = check_state(e);  // (the guard of ge_step, before anything is launched)
-  if (rc == GE_OK) rc = ge_policy_sample(e, logits, policy_seed, greedy, actions, logp, entropy, stream);
-  return rc == GE_OK ? ge_step(e, actions, stream) : rc;
+  return ge_policy_step_as(e, logits, GE_LOGITS_F32, 1.0f, policy_seed, greedy, actions, logp, entropy, stream);
 }
 
 extern "C" int ge_random_rollout(ge_engine *e, uint64_t policy_seed, int32_t n_steps, int64_t *scratch, void *stream) {

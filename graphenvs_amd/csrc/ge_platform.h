@@ -97,6 +97,61 @@ GE_DEV int ge_clz32(uint32_t v) { return v ? (int)__builtin_clz(v) : 32; }
   hipFuncSetAttribute((const void *)(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes))
 #endif
 
+// 16-bit floating-point storage (both builds): the words of a bfloat16 / float16 tensor, converted at the load and at the store.
+// Up: exact.  Down: round to nearest even for every finite value; NaN stays NaN (which one is not defined).  The HIP build uses the
+// hardware conversions (v_cvt_f32_f16 / v_cvt_f16_f32, v_cvt_pk_bf16_f32; bfloat16 up is a shift); the CPU harness's compiler has
+// neither _Float16 nor __bf16 and converts on the bits -- the same values (tests/test_policy_dtype.py walks all 65 536 patterns of
+// both types and a million float32 values against torch).
+struct ge_bf16 { uint16_t u; };
+struct ge_f16 { uint16_t u; };
+GE_DEV float ge_bits_f32(uint32_t u) { float f; __builtin_memcpy(&f, &u, 4); return f; }
+GE_DEV uint32_t ge_f32_bits(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
+GE_DEV float ge_to_f32(ge_bf16 h) { return ge_bits_f32((uint32_t)h.u << 16); }
+#ifdef GE_EMU
+GE_DEV ge_bf16 ge_from_f32(float f, ge_bf16) {
+  uint32_t u = ge_f32_bits(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return ge_bf16{(uint16_t)((u >> 16) | 0x40u)};
+  u += 0x7fffu + ((u >> 16) & 1u);  // (half of the dropped 16 bits, a tie towards the even word; a carry runs on into the exponent)
+  return ge_bf16{(uint16_t)(u >> 16)};
+}
+GE_DEV float ge_to_f32(ge_f16 h) {
+  const uint32_t s = (uint32_t)(h.u & 0x8000u) << 16, e = (h.u >> 10) & 31u, m = h.u & 0x3ffu;
+  if (e == 31u) return ge_bits_f32(s | 0x7f800000u | (m << 13));
+  if (e != 0u) return ge_bits_f32(s | ((e + 112u) << 23) | (m << 13));
+  return ge_bits_f32(s | ge_f32_bits((float)m * 0x1p-24f));  // subnormal (and zero): m quanta of 2^-24
+}
+GE_DEV ge_f16 ge_from_f32(float f, ge_f16) {
+  const uint32_t u = ge_f32_bits(f), a = u & 0x7fffffffu;
+  const uint16_t s = (uint16_t)((u >> 16) & 0x8000u);
+  if (a > 0x7f800000u) return ge_f16{(uint16_t)(s | 0x7e00u)};
+  if (a >= 0x38800000u) {  // 2^-14 and above: a float16 normal, or past its range
+    uint32_t r = a - 0x38000000u;  // exponent rebias 127 -> 15
+    r += 0xfffu + ((r >> 13) & 1u);  // (half of the dropped 13 bits, a tie towards the even word; a carry runs on into the exponent)
+    r >>= 13;
+    return ge_f16{(uint16_t)(s | (r >= 0x7c00u ? 0x7c00u : r))};
+  }
+  // below 2^-14: a count of 2^-24 quanta.  0.5f + |f| has exactly that quantum, so the float32 add does the rounding to nearest even
+  return ge_f16{(uint16_t)(s | (ge_f32_bits(ge_bits_f32(a) + 0.5f) - 0x3f000000u))};
+}
+#else
+GE_DEV ge_bf16 ge_from_f32(float f, ge_bf16) { const __bf16 b = (__bf16)f; ge_bf16 h; __builtin_memcpy(&h.u, &b, 2); return h; }
+// (the float32 value passes through an opaque move on either side of the float16 conversion: without it the compiler folds a float32
+// multiply next to the conversion into one v_fma_mix* instruction -- fma(a, b, 0) converted -- whose words differed from multiply-
+// then-convert on the MI355X in 3 gradient elements of 1 500; with it the multiply and v_cvt_f16_f32 / v_cvt_f32_f16 stay apart)
+GE_DEV float ge_to_f32(ge_f16 h) { _Float16 v; __builtin_memcpy(&v, &h.u, 2); float f = (float)v; asm("" : "+v"(f)); return f; }
+GE_DEV ge_f16 ge_from_f32(float f, ge_f16) { asm("" : "+v"(f)); const _Float16 v = (_Float16)f; ge_f16 h; __builtin_memcpy(&h.u, &v, 2); return h; }
+#endif
+GE_DEV float ge_to_f32(float f) { return f; }
+GE_DEV float ge_from_f32(float f, float) { return f; }
+// v * s, s the same in every lane, as ONE v_mul_f32 whose result replaces v in its register (round to nearest even like the `*` it
+// stands for, and never contracted with a neighbour).  For a multiply applied to many loaded values at once -- a row held in
+// registers: the compiler otherwise keeps loaded values and products apart and the kernel's register count rises with the row
+#ifdef GE_EMU
+GE_DEV float ge_mul_f32_inplace(float v, float s) { return v * s; }
+#else
+GE_DEV float ge_mul_f32_inplace(float v, float s) { asm("v_mul_f32 %0, %1, %0" : "+v"(v) : "s"(s)); return v; }
+#endif
+
 // Issue priority by role (ge_wave_priority; both builds see these, the CPU harness ignores them).  A shard's step runs at the
 // latency of its own launch chain, beside the other shards' kernels on the same SIMDs: a kernel that is a handful of waves doing
 // dependent round trips outranks the feature kernels, which are the throughput tenants and fill the issue slots the others leave.

@@ -21,6 +21,17 @@
 // gl counts as 0 where the action a* is -1, out of range or masked out (the forward's logp is -inf there).  A row held in registers
 // is stored from them, chunk after chunk (4 B of logit and 1 B of mask read, 4 B written per element); a longer row is read a
 // third time.  Every element of every row is written; lanes and chunks past the row's end store nothing.
+//
+// Storage type and scale (the *_as entry points; ge_policy_sample and its kin are float32 with scale 1.0f).  The logits are float32,
+// bfloat16 or float16 words, the kernels are instantiated per type.  An element is converted to float32 (exact) and multiplied by
+// io.scale, the product rounded to float32 ONCE: that product is l everywhere above -- mx, d, w, Z, the prefix sums, the greedy
+// comparison and the writer lane's re-read of x[a] -- so a 16-bit launch equals the float32 launch on float(x) * scale bit for bit
+// (x 1.0f is exact: the float32 path with scale 1 computes what it did before the scale existed).  The gradient is stored in the
+// logits' type: round_to_nearest_even(g * scale), g the float32 gradient above, a masked element +0.0 (a VALID element whose gradient
+// is zero may carry either sign, as in float32: the row with one valid action gets gl * (1 - 1), -0.0 for gl < 0).  One load helper and one store
+// helper (ge_pol_load / ge_pol_store) are the only places that know the type; the (chunk, lane) mapping and every tree are the
+// float32 kernel's.  16-bit rows start at element i * A, 2-byte aligned only: every lane loads and stores single 2-byte words
+// (2 B of logit and 1 B of mask read, 2 B written per element).
 #pragma once
 #include <math.h>
 
@@ -36,7 +47,7 @@ enum { GE_POL_SAMPLE = 0, GE_POL_GREEDY = 1, GE_POL_EVALUATE = 2, GE_POL_MODES =
 template <int N> struct GeInt { static constexpr int value = N; };
 
 struct GePolicyIO {
-  const float *logits;    // the classes' [B_c, A_c] blocks one after the other (GeParams.policy_off)
+  const void *logits;     // the classes' [B_c, A_c] blocks one after the other (GeParams.policy_off), in the kernel's storage type
   const uint8_t *mask;    // evaluate, gradient: bool bytes in the layout of logits
   const int64_t *given;   // evaluate, gradient: the actions to score
   int64_t *actions;       // sample, greedy
@@ -44,8 +55,33 @@ struct GePolicyIO {
   uint64_t policy_seed;
   int32_t group;          // lanes per row (GePlan.pol_group)
   const float *grad_logp, *grad_entropy;  // gradient: upstream [B] of logp and entropy, NULL: zeros
-  float *grad_logits;                     // gradient: out, in the layout of logits
+  void *grad_logits;                      // gradient: out, in the layout and the storage type of logits
+  float scale;                            // every element times this, in float32, is "the logit" (1.0f: the element itself)
 };
+
+// THE load and THE store of the logits' storage type T (float, ge_bf16, ge_f16: ge_platform.h).  Load: the element as float32 (exact,
+// ge_pol_raw) times scale, ONE float32 rounding (ge_pol_scaled) -- the logit of everything below; ge_pol_load is the two together,
+// for a single element.  Where several elements are loaded back to back (the chunks of a row in registers, the blocks of a longer
+// row) the place of the multiplies is chosen per kernel, by measurement (MI355X, against the kernel without a scale):
+//  - evaluate, row in registers: the ge_pol_raw loads first, each ge_pol_scaled in the loop that first uses the elements, behind the
+//    chunk's validity bit.  The in-place multiply is an asm statement and the compiler keeps it where the source has it.  Inside
+//    the load loop it sat between the loads with an s_waitcnt vmcnt(0) in front, and a row of two chunks made two memory round trips
+//    instead of one (18.6 us instead of 16.8 for three classes of 12 / 64 / 100 actions, 48.4 instead of 46.4 at 2 048 actions).
+//    In a loop of its own behind the loads the kernel takes 116 VGPRs, in front of the validity bit 80 / 82, behind it the 78 / 80
+//    of the kernel without a scale;
+//  - sample, greedy: inside the load loop.  Their validity loop holds a ds_bpermute per chunk, and an asm statement between them
+//    keeps the compiler from issuing those back to back (2 048 actions: 99.2 us instead of 93.2); their loads carry no mask bytes;
+//  - gradient: inside the load loop, as a plain multiply (in-place: 108 us instead of 80 at 2 048 actions);
+//  - a block of a longer row: eight loads, then eight multiplies.
+// Store: the gradient with respect to that logit times scale (one float32 multiply), rounded to T to nearest even.
+// The multiply of the forward kernels is ge_mul_f32_inplace (ge_platform.h): one v_mul_f32 whose product lands in the register the
+// element was loaded into (profiles/r05_policy_dtype.txt):
+//  - written as `* scale` the float32 evaluate kernel took 89 VGPRs (91 for a multi-class engine) instead of the 78 / 80 it has without
+//    a scale, five waves per SIMD instead of six, and 37.0 us instead of 33.2 at 65 536 rows of 64 actions;
+template <class T> GE_DEV float ge_pol_raw(const T *x, int64_t k) { return ge_to_f32(x[k]); }
+template <int MODE> GE_DEV float ge_pol_scaled(float raw, float scale) { return MODE == GE_POL_GRAD ? raw * scale : ge_mul_f32_inplace(raw, scale); }
+template <int MODE, class T> GE_DEV float ge_pol_load(const T *x, int64_t k, float scale) { return ge_pol_scaled<MODE>(ge_pol_raw(x, k), scale); }
+template <class T> GE_DEV void ge_pol_store(T *out, int64_t k, float g, float scale) { out[k] = ge_from_f32(g * scale, T()); }
 
 // lane group of a row: lanes [lane - g, lane - g + G), G a power of two.  Every lane of the group executes these.
 GE_DEV float ge_shfl_f32(float v, int src) {
@@ -104,7 +140,7 @@ GE_DEV float ge_pol_grad_at(const GePolGradRow &c, float xj, bool v, int idx) {
 }
 
 // The body of ge_k_policy_head<RAGGED, MODE> and, with MODE = GE_POL_GRAD, of ge_k_policy_grad<RAGGED>.
-template <bool RAGGED, int MODE>
+template <bool RAGGED, int MODE, class T>
 GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO &io) {
   constexpr bool EVAL = MODE == GE_POL_EVALUATE || MODE == GE_POL_GRAD;  // validity from the caller's bytes, nothing of the episode read
   const int tid = ge_tid(), lane = tid & 63;
@@ -122,7 +158,8 @@ GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO 
   const GeParams &P = RAGGED ? R.classes[cls] : PG;
   const int i = ig - lo, A = P.A, AW = P.AW;
   const int64_t row = P.policy_off + (int64_t)i * A;
-  const float *x = io.logits + row;
+  const T *x = (const T *)io.logits + row;
+  const float scale = io.scale;
   const uint8_t *mbytes = EVAL ? io.mask + row : nullptr;
   const uint64_t *mb = P.buf.mask_bits + (int64_t)i * AW;
   const int nch = G < 64 ? 1 : (A + 63) >> 6;  // (G < 64: every row of the launch fits its group)
@@ -149,7 +186,7 @@ GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO 
     if (ok && io.grad_logp) gr.gl = io.grad_logp[ig];
     if (io.grad_entropy) gr.gh = io.grad_entropy[ig];
   }
-  float *gout = MODE == GE_POL_GRAD ? io.grad_logits + row : nullptr;
+  T *gout = MODE == GE_POL_GRAD ? (T *)io.grad_logits + row : nullptr;
   auto grad_row = [&]() {  // after the row pass (any, mx, Z, s1)
     if (!any) return;
     gr.mx = mx; gr.rZ = 1.0f / Z;
@@ -160,6 +197,7 @@ GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO 
   // in front of the first use.
   auto in_regs = [&](auto nc) {
     constexpr int NCH = decltype(nc)::value;
+    constexpr bool LATE = MODE == GE_POL_EVALUATE;  // where the multiply of the row's elements stands (ge_pol_scaled, above)
     float xv[NCH];
     uint8_t mv[NCH];
     uint32_t vb = 0;  // bit j: element j * G + g is a valid action
@@ -168,7 +206,7 @@ GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO 
 #pragma unroll
     for (int j = 0; j < NCH; j++) {
       const int idx = j * G + g;
-      xv[j] = x[idx < A ? idx : 0];
+      xv[j] = LATE ? ge_pol_raw(x, idx < A ? idx : 0) : ge_pol_load<MODE>(x, idx < A ? idx : 0, scale);
       if (EVAL) mv[j] = mbytes[idx < A ? idx : 0];
     }
     float m = -INFINITY;
@@ -179,6 +217,7 @@ GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO 
       if (EVAL) v = idx < A && mv[j] != 0;
       else { const uint64_t mw = ge_shfl_u64(words, gbase + j); v = idx < A && ((mw >> (idx & 63)) & 1ull) != 0ull; }
       vb |= (uint32_t)v << j;
+      if (LATE) xv[j] = ge_pol_scaled<MODE>(xv[j], scale);  // (from here on xv[j] is the logit: every use below comes after this loop)
       if (v) m = fmaxf(m, xv[j]);
     }
     mx = ge_grp_max(m, lane, G);
@@ -205,14 +244,14 @@ GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO 
       constexpr int HALF = NCH / 2;
       if (G == 64 && nch > HALF) {
 #pragma unroll
-        for (int j = 0; j < HALF; j++) gout[j * 64 + g] = gv[j];
+        for (int j = 0; j < HALF; j++) ge_pol_store(gout, j * 64 + g, gv[j], scale);
 #pragma unroll
         for (int j = HALF; j < NCH; j++)
-          if (j * 64 + g < A) gout[j * 64 + g] = gv[j];
+          if (j * 64 + g < A) ge_pol_store(gout, j * 64 + g, gv[j], scale);
       } else {
 #pragma unroll
         for (int j = 0; j < NCH; j++)
-          if (j * G + g < A) gout[j * G + g] = gv[j];
+          if (j * G + g < A) ge_pol_store(gout, j * G + g, gv[j], scale);
       }
     }
   };
@@ -234,9 +273,11 @@ GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO 
 #pragma unroll
       for (int k = 0; k < GE_POL_BLOCK; k++) {
         const int idx = (j0 + k) * 64 + lane;
-        xs[k] = x[idx < A ? idx : 0];
+        xs[k] = ge_pol_raw(x, idx < A ? idx : 0);
         if (EVAL) ms[k] = mbytes[idx < A ? idx : 0];
       }
+#pragma unroll
+      for (int k = 0; k < GE_POL_BLOCK; k++) xs[k] = ge_pol_scaled<MODE>(xs[k], scale);
     };
     auto valid_at = [&](int j0, int k) {
       const int idx = (j0 + k) * 64 + lane;
@@ -277,7 +318,7 @@ GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO 
         for (int k = 0; k < GE_POL_BLOCK; k++) gv[k] = ge_pol_grad_at(gr, xs[k], valid_at(j0, k), (j0 + k) * 64 + lane);
 #pragma unroll
         for (int k = 0; k < GE_POL_BLOCK; k++)
-          if ((j0 + k) * 64 + lane < A) gout[(j0 + k) * 64 + lane] = gv[k];
+          if ((j0 + k) * 64 + lane < A) ge_pol_store(gout, (j0 + k) * 64 + lane, gv[k], scale);
       }
     }
   }
@@ -294,17 +335,17 @@ GE_DEV void ge_pol_rows(const GeParams &PG, const GeRagged &R, const GePolicyIO 
   if (MODE == GE_POL_EVALUATE) {
     const int64_t a = io.given[ig];
     const bool ok = !idle && a >= 0 && a < (int64_t)A && mbytes[a] != 0;
-    lp = ok ? (x[a] - mx) - logf(Z) : -INFINITY;
+    lp = ok ? (ge_pol_load<MODE>(x, a, scale) - mx) - logf(Z) : -INFINITY;  // (ok: a is inside the row)
   } else {
-    if (!idle) lp = (x[act] - mx) - logf(Z);
+    if (!idle) lp = (ge_pol_load<MODE>(x, act, scale) - mx) - logf(Z);
     io.actions[ig] = idle ? -1 : (int64_t)act;
   }
   if (io.logp) io.logp[ig] = lp;
   if (io.entropy) io.entropy[ig] = ent;
 }
 
-template <bool RAGGED, int MODE>
-GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePolicyIO io) { ge_pol_rows<RAGGED, MODE>(PG, R, io); }
+template <bool RAGGED, int MODE, class T>
+GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_head(GeParams PG, GeRagged R, GePolicyIO io) { ge_pol_rows<RAGGED, MODE, T>(PG, R, io); }
 
-template <bool RAGGED>
-GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_grad(GeParams PG, GeRagged R, GePolicyIO io) { ge_pol_rows<RAGGED, GE_POL_GRAD>(PG, R, io); }
+template <bool RAGGED, class T>
+GE_KERNEL_LB(GE_POL_THREADS, 1) ge_k_policy_grad(GeParams PG, GeRagged R, GePolicyIO io) { ge_pol_rows<RAGGED, GE_POL_GRAD, T>(PG, R, io); }

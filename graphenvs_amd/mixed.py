@@ -136,17 +136,18 @@ class MixedVectorEnv:
     def sample_random_actions(self, policy_seed=0):
         return self._each(lambda m: m.sample_random_actions(policy_seed))
 
-    def sample_actions(self, logits, policy_seed=0, greedy=False):
-        """EngineHandle.sample_actions of every member: one logits tensor per member in, one (actions, logp, entropy) per member out"""
-        return self._each(lambda m, x: m.sample_actions(x, policy_seed, greedy), logits)
+    def sample_actions(self, logits, policy_seed=0, greedy=False, temperature=1.0):
+        """EngineHandle.sample_actions of every member: one logits tensor (float32, bfloat16 or float16) per member in, one
+        (actions, logp, entropy) per member out; one temperature for all"""
+        return self._each(lambda m, x: m.sample_actions(x, policy_seed, greedy, temperature=temperature), logits)
 
-    def evaluate_actions(self, logits, actions, mask):
+    def evaluate_actions(self, logits, actions, mask, temperature=1.0):
         """EngineHandle.evaluate_actions of every member: one (logp, entropy) per member"""
-        return self._each(lambda m, a: m.evaluate_actions(*a), list(zip(logits, actions, mask)))
+        return self._each(lambda m, a: m.evaluate_actions(*a, temperature=temperature), list(zip(logits, actions, mask)))
 
-    def step_policy(self, logits, policy_seed=0, greedy=False):
+    def step_policy(self, logits, policy_seed=0, greedy=False, temperature=1.0):
         """EngineHandle.step_policy of every member, returned like step(): one list per element of the step tuple"""
-        outs = self._each(lambda m, x: m.step_policy(x, policy_seed, greedy), logits)
+        outs = self._each(lambda m, x: m.step_policy(x, policy_seed, greedy, temperature=temperature), logits)
         return tuple(list(col) for col in zip(*outs))
 
     def random_rollout(self, n_steps, policy_seed=0):

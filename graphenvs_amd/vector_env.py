@@ -182,16 +182,37 @@ def slot_seeds(seed, num_envs, env_index_base, device):
     return torch.from_numpy(s.astype(np.uint32).view(np.int32)).to(device)
 
 
+# GE_LOGITS_* of include/graphenvs.h: the storage types the policy head reads logits in (and writes their gradient in)
+_LOGITS_DTYPES = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
+
+
+def policy_scale(temperature):
+    """the float32 factor the engine multiplies every logit by: ``float(np.float32(1) / np.float32(temperature))``"""
+    with np.errstate(all="ignore"):
+        try:
+            t = np.float32(temperature)
+        except (TypeError, ValueError):
+            raise ValueError(f"temperature must be a finite number > 0, got {temperature!r}") from None
+        if t.ndim != 0:
+            raise ValueError(f"temperature must be one number, got {temperature!r}")
+        scale = float(np.float32(1) / t)
+    if not (np.isfinite(t) and t > 0 and np.isfinite(scale) and scale > 0):  # (a float32 1 / t that overflows or underflows is refused too)
+        raise ValueError(f"temperature must be a finite number > 0 (and so must 1 / temperature in float32), got {temperature!r}")
+    return scale
+
+
 class _EvaluateActions(torch.autograd.Function):
-    """evaluate_actions with a gradient for the logits: ge_policy_evaluate forward, ge_policy_backward backward (one launch each).
+    """evaluate_actions with a gradient for the logits: ge_policy_evaluate_as forward, ge_policy_backward_as backward (one launch
+    each; the gradient has the logits' dtype).
     The outputs are fresh tensors -- a training step holds several evaluations alive; save_for_backward makes an in-place change of
     the logits, mask or actions before backward() torch's own error."""
 
     @staticmethod
-    def forward(ctx, x, actions, mask, env):
+    def forward(ctx, x, actions, mask, env, scale):
         logp, entropy = (torch.empty(env.num_envs, dtype=torch.float32, device=env.device) for _ in range(2))
-        env._call("ge_policy_evaluate", x.data_ptr(), mask.data_ptr(), actions.data_ptr(), logp.data_ptr(), entropy.data_ptr(), env._stream())
-        ctx.env = env
+        env._call("ge_policy_evaluate_as", x.data_ptr(), _LOGITS_DTYPES[x.dtype], scale, mask.data_ptr(), actions.data_ptr(), logp.data_ptr(),
+                  entropy.data_ptr(), env._stream())
+        ctx.env, ctx.scale = env, scale
         ctx.set_materialize_grads(False)  # (an output the loss does not use reaches backward as None, not as a tensor of zeros)
         ctx.save_for_backward(x, mask, actions)
         return logp, entropy
@@ -205,10 +226,10 @@ class _EvaluateActions(torch.autograd.Function):
         x, mask, actions = ctx.saved_tensors
         # (an upstream gradient is often an expanded stride-0 view -- the one of a .mean() loss -- or absent: NULL stands for zeros)
         up = [None if g is None else g.to(device=env.device, dtype=torch.float32).contiguous() for g in (grad_logp, grad_entropy)]
-        grad = torch.empty_like(x)  # (x is contiguous; the launch writes every element.  The locals outlive the enqueue below)
-        env._call("ge_policy_backward", x.data_ptr(), mask.data_ptr(), actions.data_ptr(), *(None if g is None else g.data_ptr() for g in up),
-                  grad.data_ptr(), env._stream())
-        return grad, None, None, None
+        grad = torch.empty_like(x)  # (x is contiguous, the gradient has its dtype; the launch writes every element.  The locals outlive the enqueue below)
+        env._call("ge_policy_backward_as", x.data_ptr(), _LOGITS_DTYPES[x.dtype], ctx.scale, mask.data_ptr(), actions.data_ptr(),
+                  *(None if g is None else g.data_ptr() for g in up), grad.data_ptr(), env._stream())
+        return grad, None, None, None, None
 
 
 class EngineHandle:
@@ -276,7 +297,7 @@ class EngineHandle:
                                 eval_logp=f(torch.float32), eval_entropy=f(torch.float32))
         return self._policy
 
-    def sample_actions(self, logits, policy_seed=0, greedy=False):
+    def sample_actions(self, logits, policy_seed=0, greedy=False, temperature=1.0):
         """Masked categorical draw of every slot from the caller's logits, in one launch: ``(actions int64 [B], logp float32 [B],
         entropy float32 [B])`` -- what ``Categorical(logits=logits.masked_fill(~info['mask'], -inf))`` gives through sample(),
         log_prob() and entropy().  ``logits``: any float32 tensor on the engine's device with one element per (slot, action) in the
@@ -284,15 +305,21 @@ class EngineHandle:
         wrong element count, dtype or device raises.  The draw is a function of (policy_seed, global slot, the slot's transition
         count); ``greedy=True`` takes the valid action of largest logit.  A slot with no valid action and a frozen slot return
         -1, 0, 0.  The three tensors are allocated once per engine and overwritten by the next sample_actions() / step_policy():
-        ``.clone()`` what a rollout buffer keeps, as with step()."""
-        x = self._policy_input(logits, "logits", (torch.float32,))
+        ``.clone()`` what a rollout buffer keeps, as with step().
+
+        ``logits`` may also be bfloat16 or float16 (what a network under autocast emits): the kernel converts in registers, no
+        ``.float()`` pass is needed.  ``temperature`` (a finite number > 0) divides the logits: the engine multiplies every element,
+        as float32, by ``scale = float(np.float32(1) / np.float32(temperature))`` -- one float32 rounding -- and the result is
+        bit for bit that of ``sample_actions(logits.float() * scale)``; 1.0 changes nothing."""
+        x = self._policy_input(logits, "logits", tuple(_LOGITS_DTYPES))
+        scale = policy_scale(temperature)
         o = self._policy_buffers()
         self._policy_keepalive = x
-        self._call("ge_policy_sample", x.data_ptr(), int(policy_seed), int(bool(greedy)), o["actions"].data_ptr(), o["logp"].data_ptr(),
-                   o["entropy"].data_ptr(), self._stream())
+        self._call("ge_policy_sample_as", x.data_ptr(), _LOGITS_DTYPES[x.dtype], scale, int(policy_seed), int(bool(greedy)),
+                   o["actions"].data_ptr(), o["logp"].data_ptr(), o["entropy"].data_ptr(), self._stream())
         return o["actions"], o["logp"], o["entropy"]
 
-    def evaluate_actions(self, logits, actions, mask):
+    def evaluate_actions(self, logits, actions, mask, temperature=1.0):
         """``(logp, entropy)`` of stored ``actions`` [B] under stored masks: the re-scoring of a PPO / A2C update.  ``mask``: bool or
         uint8, one element per logit -- what info['mask'] (``mask_flat``) held when the actions were drawn, cloned into the rollout
         buffer; the engine's live mask is not read.  On the logits, mask and actions of a sample_actions() call it returns that
@@ -302,30 +329,38 @@ class EngineHandle:
         Differentiable in the logits: when ``logits.requires_grad`` and grad mode is on, the same values come back in fresh tensors
         with a ``grad_fn`` whose backward is one launch (ge_policy_backward, DESIGN.md 5: masked logits get a gradient of exactly
         0.0, a row whose action scored -inf drops its logp gradient, first order only).  sample_actions() and step_policy() carry no
-        gradient: an on-policy update calls evaluate_actions() with the cloned mask and the drawn actions."""
-        x = self._policy_input(logits, "logits", (torch.float32,))
+        gradient: an on-policy update calls evaluate_actions() with the cloned mask and the drawn actions.
+
+        ``logits`` float32, bfloat16 or float16 and ``temperature`` as in sample_actions().  The gradient has the logits' dtype and
+        is taken with respect to the tensor passed in: with g the float32 gradient with respect to the scaled logit, an element is
+        ``g * scale`` (one float32 multiply) rounded to the dtype to nearest even -- what autograd gives for
+        ``evaluate_actions(logits.float() * scale, ...)``, bit for bit, without the cast and scale passes in either direction."""
+        x = self._policy_input(logits, "logits", tuple(_LOGITS_DTYPES))
+        scale = policy_scale(temperature)
         mk = self._policy_input(mask, "mask", (torch.bool, torch.uint8)).view(torch.uint8)
         if not torch.is_tensor(actions):
             actions = torch.as_tensor(np.asarray(actions, dtype=np.int64))
         a = actions.to(device=self.device, dtype=torch.int64).contiguous()
         assert a.shape == (self.num_envs,)
         if x.requires_grad and torch.is_grad_enabled():
-            return _EvaluateActions.apply(x, a, mk, self)
+            return _EvaluateActions.apply(x, a, mk, self, scale)
         o = self._policy_buffers()
         self._evaluate_keepalive = (x, mk, a)
-        self._call("ge_policy_evaluate", x.data_ptr(), mk.data_ptr(), a.data_ptr(), o["eval_logp"].data_ptr(), o["eval_entropy"].data_ptr(),
-                   self._stream())
+        self._call("ge_policy_evaluate_as", x.data_ptr(), _LOGITS_DTYPES[x.dtype], scale, mk.data_ptr(), a.data_ptr(), o["eval_logp"].data_ptr(),
+                   o["eval_entropy"].data_ptr(), self._stream())
         return o["eval_logp"], o["eval_entropy"]
 
-    def step_policy(self, logits, policy_seed=0, greedy=False):
+    def step_policy(self, logits, policy_seed=0, greedy=False, temperature=1.0):
         """sample_actions(logits, ...) and step() of the drawn actions in one call, nothing read back in between: returns what
-        step() returns, with ``info['action']``, ``info['logp']`` and ``info['entropy']`` added (the tensors of sample_actions)."""
-        x = self._policy_input(logits, "logits", (torch.float32,))
+        step() returns, with ``info['action']``, ``info['logp']`` and ``info['entropy']`` added (the tensors of sample_actions).
+        ``logits`` float32, bfloat16 or float16 and ``temperature`` as in sample_actions()."""
+        x = self._policy_input(logits, "logits", tuple(_LOGITS_DTYPES))
+        scale = policy_scale(temperature)
         assert self._was_reset, "call reset() (or inject_state()) before step_policy()"
         o = self._policy_buffers()
         self._policy_keepalive = x
-        self._call("ge_policy_step", x.data_ptr(), int(policy_seed), int(bool(greedy)), o["actions"].data_ptr(), o["logp"].data_ptr(),
-                   o["entropy"].data_ptr(), self._stream())
+        self._call("ge_policy_step_as", x.data_ptr(), _LOGITS_DTYPES[x.dtype], scale, int(policy_seed), int(bool(greedy)),
+                   o["actions"].data_ptr(), o["logp"].data_ptr(), o["entropy"].data_ptr(), self._stream())
         return self._after_step(dict(action=o["actions"], logp=o["logp"], entropy=o["entropy"]))
 
     def random_rollout(self, n_steps, policy_seed=0):

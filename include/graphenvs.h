@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define GE_ABI_VERSION 7
+#define GE_ABI_VERSION 8
 
 /* env ids of graph_envs/__init__.py:9-56 that are on the hot path */
 enum {
@@ -45,6 +45,14 @@ enum {
   GE_E_TOOBIG = -4,      /* per-env graph does not fit the LDS-resident reset kernel */
   GE_E_STATE = -5        /* call order: the engine holds no episode yet (ge_reset / ge_inject_state first), or autoreset needs
                             generator states that were never seeded (ge_reset, or ge_inject_state with seeds) */
+};
+
+/* storage type of the logits (and of their gradient) handed to the policy head's *_as entry points */
+enum {
+  GE_LOGITS_F32 = 0,   /* float32 */
+  GE_LOGITS_BF16 = 1,  /* bfloat16 words */
+  GE_LOGITS_F16 = 2,   /* IEEE float16 words */
+  GE_LOGITS_DTYPES = 3 /* (their number) */
 };
 
 /* slot_rec[2*i + 1]: packed scalar state of slot i */
@@ -318,6 +326,29 @@ int ge_policy_backward(ge_engine *e, const float *logits, const uint8_t *mask, c
  * Same call-order guard as ge_step. */
 int ge_policy_step(ge_engine *e, const float *logits, uint64_t policy_seed, int32_t greedy,
                    int64_t *actions, float *logp, float *entropy, void *stream);
+
+/* The policy head on float32, bfloat16 or float16 logits with a scale: ge_policy_sample / _evaluate / _backward / _step are these
+ * calls with GE_LOGITS_F32 and scale 1.0f, and everything said there holds here.
+ *  - logits: words of logits_dtype (GE_LOGITS_*), contiguous, in the layout above (a 16-bit row starts at element i * A: 2-byte
+ *    alignment is all that is needed); scale: float32, finite and > 0 -- the reciprocal of a sampling temperature;
+ *  - an element is converted to float32 (exact) and multiplied by scale, the product rounded to float32 once; that product is the
+ *    logit l of the arithmetic above, everywhere (maximum, sums, prefix sums, the greedy comparison, logp).  Hence a 16-bit call on
+ *    (x, scale) returns bit for bit what the float32 call returns on the float32 array float(x) * scale, and float32 with scale
+ *    1.0f what it returned before the scale existed;
+ *  - ge_policy_backward_as: grad_logits has logits_dtype and the layout of logits.  With g the float32 gradient of
+ *    ge_policy_backward with respect to the scaled logit, the element is round_to_nearest_even(g * scale) (one float32 multiply;
+ *    the identity rounding for float32), +0.0 for a masked element; every element of every row is written.  A valid element whose
+ *    gradient is zero keeps the sign float32 gives it: the row with one valid action holds gl * (1 - 1), -0.0 where gl < 0.  This is what
+ *    differentiating float(x) * scale through the float32 path and casting the gradient back to logits_dtype gives, bit for bit;
+ *  - GE_E_BADARG for a logits_dtype outside GE_LOGITS_* and for a scale that is not finite or not > 0. */
+int ge_policy_sample_as(ge_engine *e, const void *logits, int32_t logits_dtype, float scale, uint64_t policy_seed, int32_t greedy,
+                        int64_t *actions, float *logp, float *entropy, void *stream);
+int ge_policy_evaluate_as(ge_engine *e, const void *logits, int32_t logits_dtype, float scale, const uint8_t *mask,
+                          const int64_t *actions, float *logp, float *entropy, void *stream);
+int ge_policy_backward_as(ge_engine *e, const void *logits, int32_t logits_dtype, float scale, const uint8_t *mask,
+                          const int64_t *actions, const float *grad_logp, const float *grad_entropy, void *grad_logits, void *stream);
+int ge_policy_step_as(ge_engine *e, const void *logits, int32_t logits_dtype, float scale, uint64_t policy_seed, int32_t greedy,
+                      int64_t *actions, float *logp, float *entropy, void *stream);
 
 /* n_steps x (sample, step[, autoreset]) without host involvement between launches.  actions_scratch [B] int64 is
  * only needed by env types without a fused policy+step kernel (it may be NULL otherwise). */
