@@ -397,6 +397,11 @@ GE_DEV void ge_features_generic_env(const GeParams &P, int env, int part, int np
 #define GE_F64_L2POP 1  // level 2 of a search takes its path counts as popcounts: every node of level 1 has one path, so sigma(v) =
                         // |adj(v) & level 1| without a set-bit loop (0: the pull of the other levels; the same bytes either way)
 #endif
+#ifndef GE_F64_PLANES
+#define GE_F64_PLANES 1  // with GE_F64_L2POP: level 3 takes its path counts from three bit planes of the level-2 counts, Q_b = the nodes of
+                         // level 2 whose count has bit b, as sigma(v) = sum of 2^b |adj(v) & Q_b| -- where no count of the wave's eight
+                         // searches is above 7 (0: the pull; the same bytes either way)
+#endif
 #define GE_F64_THREADS 256
 #define GE_F64_WAVES 4
 #define GE_F64_SB 8                      // sources of a wave's sub-batch: eight lanes each
@@ -575,20 +580,47 @@ GE_DEV void ge_f64_walk_env(const GeParams &P, int env, int *ovf_flag, int32_t *
     // level 1 is the source's neighbours: one path each, no pull (a trip of the loop below for every search otherwise)
     { const int lo = lstrow[1], hi = Dw >= 1 ? (int)lstrow[2] : lo; for (int k = lo + o; k < hi; k += 8) sigrow[ordrow[k]] = 1; }  // (Dw == 0: no search of this wave has a level 1, lstrow[2] was not written)
     const bool deep = ge_ballot(ovf) != 0ull;  // the slot goes to the generic kernel: skip the pulls (their level arrays would overrun)
+    bool planes = false;  // (wave-uniform) level 3 has its counts from the bit planes of level 2: the pulls start at level 4
 #if GE_F64_L2POP
     // level 2: every neighbour in level 1 brings one path -- a popcount, no set-bit loop, no count read (so beside the writes of level 1)
     if (Dw >= 2 && !deep && !(GE_F64_ABL & 1)) {
       const uint64_t l1 = lvl[GE_F64_SB + sl];
+#if GE_F64_PLANES
+      uint32_t qlo[3] = {0u, 0u, 0u}, qhi[3] = {0u, 0u, 0u}, mx = 0u;  // this lane's part of Q_0 .. Q_2; the OR of its counts
+#endif
       for (int k = lstrow[2] + o, hi = lstrow[3]; k < hi; k += 8) {
         const int v = ordrow[k]; const uint32_t acc = (uint32_t)ge_popc64(abits[v] & l1);
         sigrow[v] = (uint8_t)acc;
         if (GE_F64_INV < 64 && acc >= (uint32_t)GE_F64_INV) ovf = true;  // (below 64: the table has every reciprocal as shipped)
+#if GE_F64_PLANES
+        const uint64_t vb = 1ull << v; const uint32_t blo = (uint32_t)vb, bhi = (uint32_t)(vb >> 32);
+#pragma unroll
+        for (int b = 0; b < 3; b++) { const uint32_t m = 0u - ((acc >> b) & 1u); qlo[b] |= m & blo; qhi[b] |= m & bhi; }
+        mx |= acc;
+#endif
       }
+#if GE_F64_PLANES
+      // level 3 from the planes: sigma(v) = sum over b of 2^b |adj(v) & Q_b| -- integers, exact in any order; a node of level 3 has no
+      // neighbour above level 2 and Q_b holds nodes of level 2 only, so no mask with the level set.  No count of level 2 is read from
+      // LDS: beside the writes of levels 1 and 2.  A wave-round with a level-2 count above 7 (a fourth plane) keeps the pull.
+      planes = Dw >= 3 && ge_ballot(mx > 7u) == 0ull;
+      if (planes) {
+        uint64_t q[3];
+#pragma unroll
+        for (int b = 0; b < 3; b++) q[b] = ((uint64_t)ge_oct_or32(qhi[b]) << 32) | (uint64_t)ge_oct_or32(qlo[b]);
+        for (int k = lstrow[3] + o, hi = lstrow[4]; k < hi; k += 8) {
+          const int v = ordrow[k]; const uint64_t a = abits[v];
+          const uint32_t acc = (uint32_t)ge_popc64(a & q[0]) + 2u * (uint32_t)ge_popc64(a & q[1]) + 4u * (uint32_t)ge_popc64(a & q[2]);
+          sigrow[v] = (uint8_t)(acc < 255u ? acc : 255u);
+          if (acc >= (uint32_t)GE_F64_INV) ovf = true;  // no reciprocal in the table: the generic kernel takes the slot
+        }
+      }
+#endif
     }
 #endif
     ge_wave_sync();
     // ---- (2) path counts: sigma(v) = sum of sigma(u) over v's neighbours u in the level above
-    for (int d = GE_F64_L2POP ? 3 : 2; d <= Dw && !deep && !(GE_F64_ABL & 1); d++) {
+    for (int d = !GE_F64_L2POP ? 2 : planes ? 4 : 3; d <= Dw && !deep && !(GE_F64_ABL & 1); d++) {
       const int lo = lstrow[d], hi = lstrow[d + 1];
       const uint64_t prev = lvl[(d - 1) * GE_F64_SB + sl];
       for (int k = lo + o; ge_ballot(k < hi) != 0ull; k += 8) {

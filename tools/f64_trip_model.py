@@ -1,6 +1,6 @@
 """Trip model of the two Brandes pulls of ge_f64_walk_env (ge_features.h), on the CPU: no GPU, pure Python.
 
-usage: python tools/f64_trip_model.py [--graphs 200] [--n 64] [--m 192] [--seed 1] > profiles/r10_trip_model.txt
+usage: python tools/f64_trip_model.py [--graphs 200] [--n 64] [--m 192] [--seed 1] > profiles/r12_trip_model.txt
 
 Seeded connected G(n, m) graphs (uniform edge sets, redrawn until connected).  A wave holds eight BFS sources (s = 32 r + 8 w + sl),
 eight lanes per source; lane o of a source takes the entries k = lo + o + 8 t of a level's stretch of the (level, node) order.  An
@@ -8,7 +8,10 @@ OUTER trip is one pass of the `k += 8` loop, which the wave leaves when no lane 
 GE_F64_U = 2 set-bit loop over one 32-bit half of the node's predecessor / successor set.  The wave pays the busiest lane of every
 outer trip.  Printed: mean trips per wave and round of both pulls as shipped before round 10, with the level-2 popcount
 (GE_F64_L2POP: level 2 has no inner trips), with a dependency pull over the nodes that have a successor only (built, measured and not
-shipped, profiles/README.md round 10), and with each level sorted by set size on top (not built)."""
+shipped, profiles/README.md round 10), with level 3 from bit planes of the level-2 counts (GE_F64_PLANES: level 3 has no inner trips in
+a wave-round whose largest level-2 count is at most 7), and with each level sorted by set size on top (not built).  Behind the table:
+the forward pull's trips level by level, and the distribution of the largest level-2 count of a wave-round (what the gate of
+GE_F64_PLANES lets through, and how many planes such a wave-round needs)."""
 import argparse
 import random
 
@@ -64,8 +67,14 @@ def pull(stretches):
     return outer, sum(max([max(s[8 * t:8 * t + 8], default=0) for s in stretches]) for t in range(outer))
 
 
-def wave(adj, sources, variant):
-    """variant: set of "l2pop", "leafskip", "sorted" -> ((outer, inner) forward, (outer, inner) backward)"""
+def l2max(adj, lv):
+    """the largest level-2 path count over the wave's searches (0: no search has a level 2)"""
+    return max((bin(adj[v] & l[1]).count("1") for l in lv if len(l) > 2 for v in nodes(l[2])), default=0)
+
+
+def wave(adj, sources, variant, levels=None):
+    """variant: set of "l2pop", "planes", "leafskip", "sorted" -> ((outer, inner) forward, (outer, inner) backward);
+    levels: a dict that takes the forward pull's (outer, inner) trips of this wave-round per level"""
     lv = [levels_of(adj, s) for s in sources]
     dw = max(len(l) for l in lv) - 1
     at = lambda l, d: l[d] if d < len(l) else 0
@@ -74,7 +83,12 @@ def wave(adj, sources, variant):
     for d in range(2, dw + 1):
         st = [order([inner(adj[v] & at(l, d - 1)) for v in nodes(at(l, d))]) for l in lv]
         o, i = pull(st)
-        fo, fi = fo + o, fi + (0 if d == 2 and "l2pop" in variant else i)
+        if (d == 2 and "l2pop" in variant) or (d == 3 and "planes" in variant and l2max(adj, lv) <= 7):
+            i = 0
+        fo, fi = fo + o, fi + i
+        if levels is not None:
+            po, pi = levels.get(d, (0, 0))
+            levels[d] = (po + o, pi + i)
     for d in range(dw - 1, 0, -1):
         st = []
         for l in lv:
@@ -96,8 +110,10 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     a = ap.parse_args()
     rng = random.Random(a.seed)
-    variants = [("shipped before round 10", set()), ("GE_F64_L2POP (shipped)", {"l2pop"}), ("+ successor-bearing nodes only", {"l2pop", "leafskip"}),
-                ("+ levels sorted by set size", {"l2pop", "leafskip", "sorted"})]
+    variants = [("shipped before round 10", set()), ("GE_F64_L2POP (shipped)", {"l2pop"}), ("+ level 3 from bit planes", {"l2pop", "planes"}),
+                ("+ successor-bearing nodes only", {"l2pop", "planes", "leafskip"}),
+                ("+ levels sorted by set size", {"l2pop", "planes", "leafskip", "sorted"})]
+    split, largest = {}, {}  # forward trips per level with GE_F64_L2POP alone; wave-rounds by their largest level-2 count
     tot = {name: [0, 0, 0, 0] for name, _ in variants}
     waves = leaves = pairs = depth = 0
     for _ in range(a.graphs):
@@ -106,9 +122,10 @@ def main():
             src = list(range(base, min(base + 8, a.n)))
             waves += 1
             for name, v in variants:
-                for k, x in enumerate(wave(adj, src, v)):
+                for k, x in enumerate(wave(adj, src, v, split if v == {"l2pop"} else None)):
                     tot[name][k] += x
             lv = [levels_of(adj, s) for s in src]
+            largest[l2max(adj, lv)] = largest.get(l2max(adj, lv), 0) + 1
             depth += max(len(l) for l in lv) - 1
             for l in lv:
                 for d in range(1, len(l)):
@@ -124,6 +141,16 @@ def main():
         fo, fi, bo, bi = (x / waves for x in tot[name])
         ref = ref or fi + bi
         print(f"{name:34s} {fo:10.1f} {fi:10.1f} {bo:10.1f} {bi:10.1f} {fi + bi:8.1f} {100.0 * (fi + bi) / ref - 100.0:+5.1f} %")
+    print("# forward pull with GE_F64_L2POP, per level of the pulled nodes (mean trips per wave and round)")
+    print(f"{'level':>34s} {'fwd outer':>10s} {'fwd inner':>10s}")
+    for d in sorted(split):
+        print(f"{d:34d} {split[d][0] / waves:10.1f} {split[d][1] / waves:10.1f}")
+    print("# wave-rounds by the largest level-2 path count of their eight searches (GE_F64_PLANES: three planes, open up to 7)")
+    print(f"{'largest count':>34s} {'wave-rounds':>12s} {'planes':>8s}")
+    for c in sorted(largest):
+        print(f"{c:34d} {largest[c]:12d} {('closed' if c > 7 else str(c.bit_length())):>8s}")
+    gate = sum(k for c, k in largest.items() if c <= 7)
+    print(f"# gate open in {gate} of {waves} wave-rounds ({100.0 * gate / waves:.1f} %)")
 
 
 if __name__ == "__main__":
